@@ -12,6 +12,12 @@ Launched by the driver as:
       --master-addr 127.0.0.1 bench.py --gpus N ... (one rank per GPU, RCCL)
 
 Rank 0 prints one JSON line with the whole-job aggregate GFLOP/s.
+
+A plain run sets up, warms up, times --steps steps and prints that line.
+--dump-outputs DIR also writes a fixed sample of the factor the last timed
+step produced, for comparing two builds output for output (the inputs are
+the same seeded fill on every run). --full is where measurements beyond
+the headline figure belong; there are none at present.
 """
 import argparse
 import json
@@ -27,6 +33,53 @@ def pick_grid(world):
         world, (1, world))
 
 
+def sample_plan(n, nb):
+    """The fixed, seeded sample of the factor that --dump-outputs keeps:
+    (bi, bj, rows, cols) for every diagonal nb x nb block and for up to 12
+    seeded off-diagonal blocks of the lower triangle, with up to 256 seeded
+    row and column indices inside each block."""
+    import numpy as np
+
+    rng = np.random.default_rng(20240607)
+    nblk = (n + nb - 1) // nb
+    off = [(i, j) for i in range(nblk) for j in range(i)]
+    picks = rng.permutation(len(off))[:12]
+    blocks = [(b, b) for b in range(nblk)] + sorted(off[k] for k in picks)
+    plan = []
+    for bi, bj in blocks:
+        ri = np.sort(rng.permutation(min(nb, n - bi * nb))[:256])
+        ci = np.sort(rng.permutation(min(nb, n - bj * nb))[:256])
+        plan.append((bi, bj, ri, ci))
+    return plan
+
+
+def dump_outputs(A, n, nb, algo, outdir):
+    """Write what the last timed step left in A (the Cholesky factor L) as
+    float64 .npy files. The factor is far larger than a dump may be, so
+    only sample_plan()'s entries are kept (L_block_<bi>_<bj>.npy), plus the
+    whole diagonal of L (L_diag_<bi>.npy): ~12 MB in all at the default
+    size. Entries above the diagonal are not part of L and are written as
+    zero. Each rank writes the blocks it owns."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for bi, bj, ri, ci in sample_plan(n, nb):
+        # panel storage keeps block column bj as one n x nb tile
+        tm, r0 = (0, bi * nb) if algo == "panel" else (bi, 0)
+        if not A.is_local(tm, bj):
+            continue
+        t = A.tile_numpy(tm, bj)
+        s = t[np.ix_(r0 + ri, ci)]
+        if bi == bj:
+            s = np.where(ri[:, None] >= ci[None, :], s, 0.0)
+            rows = min(nb, n - bi * nb)
+            d = np.ascontiguousarray(np.diagonal(t[r0:r0 + rows]))
+            np.save(os.path.join(outdir, f"L_diag_{bi:03d}.npy"), d)
+        np.save(os.path.join(outdir, f"L_block_{bi:03d}_{bj:03d}.npy"),
+                np.ascontiguousarray(s, dtype=np.float64))
+        del t
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -39,6 +92,13 @@ def main():
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--algo", type=str, default="auto",
                     choices=["auto", "tile", "panel"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the "
+                         "last step's factor L to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (none yet: the plain run is the whole "
+                         "benchmark)")
     args = ap.parse_args()
 
     import parsec_amd as pm
@@ -126,6 +186,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        dump_outputs(A, n, nb, algo, args.dump_outputs)
 
     flops_per_step = n**3 / 3.0 + n**2 / 2.0 + n / 6.0
     value = args.steps * flops_per_step / elapsed / 1e9  # GFLOP/s whole job

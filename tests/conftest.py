@@ -38,24 +38,45 @@ _port_locks = []  # flock fds held for the session lifetime
 _port_cache = {}  # salt -> base: repeat calls must return the same base
 
 
-def port_base(salt=0, span=64):
-    """A base with `span` consecutive bindable ports. Two safeguards:
-    ports stay BELOW the ephemeral range (32768+, where outgoing sockets
-    land), and the chosen window is reserved via a session-lifetime
-    flock so concurrent test sessions on one host never pick overlapping
-    windows (probing alone races: both sessions can see the same window
-    free before either binds)."""
+PORT_SLOT = 128  # ports per reservable window
+
+
+def _lock_slot(path):
+    """Session-lifetime exclusive flock on `path`; OSError if it is held.
+    Opened read-only (flock needs no write access), so a lock file that a
+    session of another user left behind can be taken again."""
     import fcntl
+    try:
+        fd = os.open(path, os.O_RDONLY)
+    except FileNotFoundError:
+        fd = os.open(path, os.O_RDONLY | os.O_CREAT, 0o644)
+    try:
+        fcntl.flock(fd, fcntl.LOCK_EX | fcntl.LOCK_NB)
+    except OSError:
+        os.close(fd)
+        raise
+    return fd
+
+
+def port_base(salt=0, span=64):
+    """A base with `span` (<= PORT_SLOT) consecutive bindable ports. Two
+    safeguards: ports stay BELOW the ephemeral range (32768+, where
+    outgoing sockets land), and the chosen window is reserved via a
+    session-lifetime flock so concurrent test sessions on one host never
+    pick overlapping windows (probing alone races: both sessions can see
+    the same window free before either binds). Windows are whole
+    PORT_SLOT-aligned slots with one lock file per slot, so two windows
+    either are the same slot or share no port."""
     import socket
     if salt in _port_cache:
         return _port_cache[salt]
-    WINDOW = 12000  # 20000..31999
-    start = 20000 + ((os.getpid() * 131 + salt * 977) % WINDOW)
-    for attempt in range(200):
-        base = 20000 + (start - 20000 + attempt * (span + 1)) % WINDOW
+    assert span <= PORT_SLOT, span
+    NSLOTS = 12000 // PORT_SLOT  # slots within 20000..31999
+    start = (os.getpid() * 131 + salt * 977) % NSLOTS
+    for attempt in range(NSLOTS):
+        base = 20000 + ((start + attempt) % NSLOTS) * PORT_SLOT
         try:
-            lf = open(f"/tmp/.pa_test_ports_{base}.lock", "w")
-            fcntl.flock(lf, fcntl.LOCK_EX | fcntl.LOCK_NB)
+            lf = _lock_slot(f"/tmp/.pa_test_slot_{base}.lock")
         except OSError:
             continue
         ok = True
@@ -78,5 +99,5 @@ def port_base(salt=0, span=64):
             _port_locks.append(lf)  # released automatically at exit
             _port_cache[salt] = base
             return base
-        lf.close()  # releases the flock; window is occupied anyway
+        os.close(lf)  # releases the flock; window is occupied anyway
     raise RuntimeError("no free port range found")

@@ -17,7 +17,26 @@ WORKER = os.path.join(HERE, "_dist_worker.py")
 
 from conftest import port_base
 
-_next_port = [port_base()]
+# every test below takes its ports from this one window: 126 in all
+_next_port = [port_base(span=128)]
+
+
+def communicate_all(procs, timeout=180):
+    """Wait for every worker and return their outputs. A worker that dies
+    leaves its peers blocked on it, so on a timeout all are ended and the
+    failure shows every worker's output, the dead one's error included."""
+    outs = []
+    try:
+        for pr in procs:
+            outs.append(pr.communicate(timeout=timeout)[0].decode())
+    except subprocess.TimeoutExpired:
+        for pr in procs:
+            pr.kill()
+        outs = [pr.communicate()[0].decode() for pr in procs]
+        report = "\n".join(f"--- rank {r} (exit {pr.returncode}):\n{o}"
+                           for r, (pr, o) in enumerate(zip(procs, outs)))
+        pytest.fail(f"workers still running after {timeout} s:\n{report}")
+    return outs
 
 
 def run_world(world, tmpdir, p, q, n=256, nb=64):
@@ -32,11 +51,9 @@ def run_world(world, tmpdir, p, q, n=256, nb=64):
         procs.append(subprocess.Popen([sys.executable, WORKER], env=env,
                                       stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT))
-    outs = []
-    for pr in procs:
-        out, _ = pr.communicate(timeout=180)
-        outs.append(out.decode())
-        assert pr.returncode == 0, f"worker failed:\n{out.decode()}"
+    outs = communicate_all(procs)
+    for pr, out in zip(procs, outs):
+        assert pr.returncode == 0, f"worker failed:\n{out}"
     # assemble
     pre = np.zeros((n, n))
     post = np.zeros((n, n))
@@ -76,9 +93,8 @@ def test_distributed_qr(tmp_path):
         procs.append(subprocess.Popen([sys.executable, WORKER], env=env,
                                       stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT))
-    for pr in procs:
-        out, _ = pr.communicate(timeout=180)
-        assert pr.returncode == 0, f"worker failed:\n{out.decode()}"
+    for pr, out in zip(procs, communicate_all(procs)):
+        assert pr.returncode == 0, f"worker failed:\n{out}"
     pre = np.zeros((n, n))
     post = np.zeros((n, n))
     for r in range(world):
@@ -214,9 +230,8 @@ def test_distributed_lu(tmp_path):
         procs.append(subprocess.Popen([sys.executable, WORKER], env=env,
                                       stdout=subprocess.PIPE,
                                       stderr=subprocess.STDOUT))
-    for pr in procs:
-        out, _ = pr.communicate(timeout=180)
-        assert pr.returncode == 0, f"worker failed:\n{out.decode()}"
+    for pr, out in zip(procs, communicate_all(procs)):
+        assert pr.returncode == 0, f"worker failed:\n{out}"
     pre = np.zeros((n, n))
     post = np.zeros((n, n))
     for r in range(world):

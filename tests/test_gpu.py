@@ -129,6 +129,44 @@ def test_bench_contract():
     assert out["dtype"] == "fp64"
 
 
+def test_bench_dump_outputs(gctx, tmp_path):
+    """bench.py --dump-outputs writes its seeded sample of the factor as
+    float64 arrays, and they are the Cholesky factor of the bench input
+    (same bound as test_gpu_cholesky_numerics: same matrix, same size)."""
+    import bench
+    n, nb = 2048, 256
+    r = subprocess.run(
+        [sys.executable, os.path.join(REPO, "bench.py"), "--matrix-size",
+         str(n), "--tile", str(nb), "--steps", "1", "--warmup", "0",
+         "--dump-outputs", str(tmp_path)],
+        capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads([l for l in r.stdout.splitlines()
+                      if l.startswith("{")][-1])
+    assert out["steps"] == 1 and out["ms_per_step"] > 0
+    A = pm.TiledMatrix(gctx, n, n, nb, nb, 1, 1)
+    tp = pm.Dtd(gctx)
+    pm.insert_spd_fill(tp, A, 42)
+    tp.wait()
+    M = assemble_lower(A, n, nb)
+    L0 = np.linalg.cholesky(np.tril(M) + np.tril(M, -1).T)
+    plan = bench.sample_plan(n, nb)
+    assert len(plan) == n // nb + 12
+    expect = {}
+    for bi, bj, ri, ci in plan:
+        expect[f"L_block_{bi:03d}_{bj:03d}.npy"] = \
+            L0[np.ix_(bi * nb + ri, bj * nb + ci)]
+        if bi == bj:
+            expect[f"L_diag_{bi:03d}.npy"] = \
+                np.diag(L0)[bi * nb:(bi + 1) * nb]
+    assert sorted(os.listdir(tmp_path)) == sorted(expect)
+    for name, ref in expect.items():
+        got = np.load(os.path.join(tmp_path, name))
+        assert got.dtype == np.float64 and got.shape == ref.shape, name
+        err = np.abs(got - ref).max()
+        assert err < 1e-8, f"{name}: max err {err}"
+
+
 def test_eviction_under_memory_pressure():
     """Force LRU eviction+writeback with a hard HBM cap smaller than the
     working set; the factorization must still be numerically correct."""
@@ -264,16 +302,17 @@ del A, B, ctx
     assert r.returncode == 0, r.stdout + r.stderr
 
 
-def test_gpu_stream_spans_in_trace():
+def test_gpu_stream_spans_in_trace(tmp_path):
     """Per-exec-stream device spans (hipEvent-timed) land in the binary
     trace as kind-7 records with tid = 1000+stream (reference parity:
     per-GPU profiling streams, device_cuda_module.c:509-530)."""
     import struct as st
+    trace = str(tmp_path / "span_trace")
     code = f"""
 import numpy as np, sys, json, struct
 sys.path.insert(0, {REPO!r})
 import parsec_amd as pm
-pm.param_set("profile_filename", "/tmp/span_trace")
+pm.param_set("profile_filename", {trace!r})
 ctx = pm.Context(nworkers=2, rank=0, world=1)
 n, nb = 2048, 512
 A = pm.TiledMatrix(ctx, n, n, nb, nb, 1, 1)
@@ -282,7 +321,7 @@ tp2 = pm.Dtd(ctx); pm.insert_potrf(tp2, A); tp2.wait()
 st = ctx.gpu_stats()
 assert st["bytes_required"] > 0
 del tp, tp2, A, ctx  # keep_alive: the context (and trace dump) waits on them
-with open("/tmp/span_trace.0", "rb") as f:
+with open({trace!r} + ".0", "rb") as f:
     assert f.readline().strip() == b"PABT1"
     hdr = json.loads(f.readline())
     raw = f.read()
