@@ -27,6 +27,7 @@ def main():
           "sched_bind (0|1|numa), gpu_exec_streams, gpu_max_inflight, "
           "gpu_mem_percent, gpu_mem_limit_mb, chore_gemm (rocblas|hip), "
           "chore_syrk (hip|dgemm|syrkx), chore_potrf (hip|rocsolver), "
+          "chore_potrf_syrk (hip|rocblas), chore_trsm_inv (hip|rocblas), "
           "chore_qr (hand|rocsolver), qr_algo (house|bcgs), trsm_variant "
           "(invgemm|rocblas), dtd_window_size, comm_kind (tcp|rccl), "
           "comm_max_inflight, comm_send_reserve, bcast_tree "

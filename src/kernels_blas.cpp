@@ -173,6 +173,9 @@ static void cpu_gemm(Task& t) {
 
 void launch_dsyrk_v2(int n, int k, const double* A, int lda, double* C,
                      int ldc, hipStream_t stream);  // kernels_hip.cpp
+void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
+                      int ldw, double* X, int ldx,
+                      hipStream_t stream);  // kernels_hip.cpp
 
 // ------------------------------------------------------------------ GPU chores
 // One rocBLAS handle PER EXEC STREAM: rocBLAS/rocSOLVER keep device
@@ -202,7 +205,15 @@ void launch_potf2(double* A, int n, int ld, hipStream_t stream);  // kernels_hip
 // Blocked tile POTRF: 128-wide LDS panel factorization (hand kernel) +
 // rocBLAS panel-TRSM + trailing SYRK, all in-order on the task's stream.
 // Critical-path op: measured ~3x faster than rocsolver_dpotrf at nb=2048.
+// The trailing update runs on the hand triangular MFMA kernel
+// (launch_dsyrk_v2: lower block set only, one launch per panel; glds path
+// when the trailing size is a multiple of 128, bounds-checked path
+// otherwise) instead of rocblas_dsyrk's k=128 decomposition into several
+// small Tensile + syrkx launches per panel. It also writes the upper half
+// of the trailing diagonal 128-blocks, which nothing reads.
+// PARSEC_MCA_chore_potrf_syrk=rocblas restores the library update.
 static void gpu_potrf_blocked(Task& t, GpuTaskCtx& g) {
+  static const bool syrk_hip = param_str("chore_potrf_syrk", "hip") == "hip";
   const TileArgs& a = t.arg<TileArgs>();
   double* A = (double*)t.dev_ptr[0];
   const int n = a.n, ld = a.ld;
@@ -220,6 +231,10 @@ static void gpu_potrf_blocked(Task& t, GpuTaskCtx& g) {
                              rocblas_diagonal_non_unit, rest, jb, &one, Ajj,
                              ld, Aij, ld) == rocblas_status_success);
       double* Att = A + (size_t)(j + jb) * ld + j + jb;
+      if (syrk_hip) {
+        launch_dsyrk_v2(rest, jb, Aij, ld, Att, ld, g.stream);
+        continue;
+      }
       PA_CHECK(rocblas_dsyrk(h, rocblas_fill_lower, rocblas_operation_none,
                              rest, jb, &mone, Aij, ld, &one, Att,
                              ld) == rocblas_status_success);
@@ -291,7 +306,9 @@ static void gpu_trtri(Task& t, GpuTaskCtx& g) {
 // TRSM via the per-step inverse: B <- B * W^T is one full-rate DGEMM
 // instead of rocBLAS dtrsm's ~44-kernel decomposition (measured ~9 TF vs
 // ~60-75 TF for dgemm at these tile sizes). W is computed once per panel
-// step and broadcast like the diagonal tile.
+// step and broadcast like the diagonal tile. By default the product runs on
+// the triangular-aware hand kernel (launch_dtrmm_rlt, half the flops);
+// PARSEC_MCA_chore_trsm_inv=rocblas keeps the dense dgemm.
 static void* stream_scratch(GpuTaskCtx& g, size_t bytes) {
   static thread_local std::map<void*, std::pair<void*, size_t>> bufs;
   auto& e = bufs[(void*)g.stream];
@@ -313,12 +330,22 @@ static void gpu_trsm_inv(Task& t, GpuTaskCtx& g) {
   // The old buffer returns to the pool only after the kernel completes
   // (deferred free through the engine's retire path).
   double* X = (double*)g.engine->dev_alloc(bd->bytes);
-  const double one = 1.0, zero = 0.0;
-  rocblas_status s = rocblas_dgemm(
-      blas_handle(g), rocblas_operation_none, rocblas_operation_transpose,
-      a.m, a.n, a.n, &one, B, a.ld, (const double*)t.dev_ptr[0], a.ld,
-      &zero, X, a.ld);
-  PA_CHECK(s == rocblas_status_success, "trsm-as-gemm failed: %d", (int)s);
+  // W is lower triangular (gpu_trtri zero-fills the rest), so half of a
+  // dense dgemm multiplies by zeros: the hand kernel cuts each output block
+  // column's K range at its diagonal block. It needs full 128x128 blocks
+  // and 16-B aligned columns; anything else takes the dense rocBLAS dgemm.
+  static const bool use_hip = param_str("chore_trsm_inv", "hip") == "hip";
+  if (use_hip && a.m % 128 == 0 && a.n % 128 == 0 && a.ld % 2 == 0) {
+    launch_dtrmm_rlt(a.m, a.n, B, a.ld, (const double*)t.dev_ptr[0], a.ld, X,
+                     a.ld, g.stream);
+  } else {
+    const double one = 1.0, zero = 0.0;
+    rocblas_status s = rocblas_dgemm(
+        blas_handle(g), rocblas_operation_none, rocblas_operation_transpose,
+        a.m, a.n, a.n, &one, B, a.ld, (const double*)t.dev_ptr[0], a.ld,
+        &zero, X, a.ld);
+    PA_CHECK(s == rocblas_status_success, "trsm-as-gemm failed: %d", (int)s);
+  }
   {
     SpinGuard gd(bd->lock);
     g.deferred_frees->emplace_back(bd->dev_ptr, bd->bytes);

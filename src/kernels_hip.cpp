@@ -18,6 +18,18 @@
 // Kernel set: dgemm_nt (C -= A*B^T — the Cholesky trailing update, also
 // reused by SYRK on the full tile), with bounds-checked edges. rocBLAS
 // remains the alternate chore; select with PARSEC_MCA_chore_gemm=hip|rocblas.
+//
+// Two more users of the same v3 structure remove work the Cholesky result
+// does not need:
+//  - TRSM-by-inverse (X = B * W^T, W = L^-1 lower triangular) runs on the
+//    V3_TRMM kind, which stops each output block column's K loop at its
+//    diagonal block: a dense dgemm spends half its flops multiplying by W's
+//    stored zeros (PARSEC_MCA_chore_trsm_inv=hip|rocblas).
+//  - the trailing update inside the blocked tile POTRF runs on the
+//    triangular SYRK kind (launch_dsyrk_v2), one launch per 128-panel and
+//    the lower block set only, instead of rocblas_dsyrk's several small
+//    k=128 launches per panel on the DAG's critical path
+//    (PARSEC_MCA_chore_potrf_syrk=hip|rocblas).
 #include <hip/hip_runtime.h>
 
 #include "device_gpu.hpp"
@@ -213,30 +225,74 @@ __global__ void k_dgemm_nt_v2(int m, int n, int k, const double* __restrict__ A,
 // async global->LDS (16 B/lane), [k][m] lane-linear LDS image (one K-row =
 // 1 KB per glds), double-buffered BK=16, one drain barrier per K-tile.
 // Full tiles only; edges fall back to v2.
-template <bool TRI>
+//
+// Three kinds share the body:
+//   V3_GEMM  C -= A B^T over the full block grid
+//   V3_SYRK  C -= A A^T over the lower-triangular block set
+//   V3_TRMM  C  = A B^T with B (n x n, k == n) lower triangular: output
+//            block column `by` only sees k < (by+1)*BN, so its K loop stops
+//            there (the diagonal K-block still reads B's strictly-upper
+//            entries, which must be stored zeros), and the epilogue stores
+//            instead of subtracting (beta = 0: C is never read).
+enum { V3_GEMM = 0, V3_SYRK = 1, V3_TRMM = 2 };
+
+// V3_TRMM block order. Block columns carry K lengths from BN to n, so the
+// order decides both the balance between XCDs (blocks are dealt to them
+// round-robin by blockIdx) and the length of the tail.
+//   TRMM_SNAKE    each XCD owns whole block columns (its blocks share the
+//                 W panel in that XCD's L2), dealt longest-first in a
+//                 boustrophedon over the XCDs so every XCD gets the same
+//                 total K; grid padded to 8 * ceil(nby/8) * nbx, padding
+//                 blocks exit at once
+//   TRMM_DESC     xcd_swizzle's contiguous chunks, longest column first
+//   TRMM_ASC      the same, shortest first (the plain GEMM order)
+//   TRMM_FLAT     no XCD remap: longest column first, its blocks spread
+//                 over all XCDs
+enum { TRMM_SNAKE = 0, TRMM_DESC = 1, TRMM_ASC = 2, TRMM_FLAT = 3 };
+
+template <int KIND>
 __launch_bounds__(512)
 __global__ void k_dgemm_nt_v3(int m, int n, int k, const double* __restrict__ A,
                               int lda, const double* __restrict__ B, int ldb,
-                              double* __restrict__ C, int ldc, int nbx) {
+                              double* __restrict__ C, int ldc, int nbx,
+                              int order) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* As = (double*)smem;                  // [2][BKD][BM]
   double* Bs = As + 2 * BKD * BM;
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int wr = wave >> 1, wc = wave & 1;
-  int id = xcd_swizzle(blockIdx.x, gridDim.x);
   int bx, by;
-  if (TRI) {
-    bx = 0;
-    int rem = id;
-    while (rem > bx) { bx++; rem -= bx; }
-    by = rem;
+  if (KIND == V3_TRMM) {
+    const int nby = n / BN;
+    if (order == TRMM_SNAKE) {
+      const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3;
+      const int round = pos / nbx;
+      const int rank = round * 8 + ((round & 1) ? 7 - xcd : xcd);
+      if (rank >= nby) return;  // padding block (whole block, before any barrier)
+      bx = pos - round * nbx;
+      by = nby - 1 - rank;
+    } else {
+      int id = order == TRMM_FLAT ? (int)blockIdx.x
+                                  : xcd_swizzle(blockIdx.x, gridDim.x);
+      bx = id % nbx;
+      by = order == TRMM_ASC ? id / nbx : nby - 1 - id / nbx;
+    }
   } else {
-    bx = id % nbx;
-    by = id / nbx;
+    int id = xcd_swizzle(blockIdx.x, gridDim.x);
+    if (KIND == V3_SYRK) {
+      bx = 0;
+      int rem = id;
+      while (rem > bx) { bx++; rem -= bx; }
+      by = rem;
+    } else {
+      bx = id % nbx;
+      by = id / nbx;
+    }
   }
   const int bm0 = bx * BM, bn0 = by * BN;
   const int ksub = lane >> 4, r16 = lane & 15;
+  const int kend = KIND == V3_TRMM ? (bn0 + BN < k ? bn0 + BN : k) : k;
 
   f64x4 acc[2][4] = {};
 
@@ -259,7 +315,7 @@ __global__ void k_dgemm_nt_v3(int m, int n, int k, const double* __restrict__ A,
 
   stage(0, 0);
   __syncthreads();
-  const int ntiles = k / BKD;
+  const int ntiles = kend / BKD;
   for (int t = 0; t < ntiles; t++) {
     if (t + 1 < ntiles) stage((t + 1) & 1, (t + 1) * BKD);
     const double* as = As + (t & 1) * BKD * BM;
@@ -291,7 +347,10 @@ __global__ void k_dgemm_nt_v3(int m, int n, int k, const double* __restrict__ A,
     for (int i = 0; i < 2; i++) {
       int row0 = bm0 + wr * 32 + i * 16 + ksub;
 #pragma unroll
-      for (int e = 0; e < 4; e++) cp[row0 + e * 4] -= acc[i][j][e];
+      for (int e = 0; e < 4; e++) {
+        if (KIND == V3_TRMM) cp[row0 + e * 4] = acc[i][j][e];
+        else cp[row0 + e * 4] -= acc[i][j][e];
+      }
     }
   }
 }
@@ -303,15 +362,13 @@ static void launch_dgemm_v2(int m, int n, int k, const double* A, int lda,
     constexpr size_t lds = 2 * BKD * (BM + BN) * 8;
     static bool attr3 = false;
     if (!attr3) {
-      hipFuncSetAttribute((const void*)k_dgemm_nt_v3<false>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipFuncSetAttribute((const void*)k_dgemm_nt_v3<true>,
+      hipFuncSetAttribute((const void*)k_dgemm_nt_v3<V3_GEMM>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       attr3 = true;
     }
     int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
-    hipLaunchKernelGGL(k_dgemm_nt_v3<false>, dim3(nbx * nby), dim3(512), lds,
-                       stream, m, n, k, A, lda, B, ldb, C, ldc, nbx);
+    hipLaunchKernelGGL(k_dgemm_nt_v3<V3_GEMM>, dim3(nbx * nby), dim3(512), lds,
+                       stream, m, n, k, A, lda, B, ldb, C, ldc, nbx, 0);
     return;
   }
   static bool attr_set = false;
@@ -338,20 +395,49 @@ void launch_dsyrk_v2(int n, int k, const double* A, int lda, double* C,
   }
   int ntb = (n + BM - 1) / BM;
   int ntiles = ntb * (ntb + 1) / 2;
-  if (n % BM == 0 && k % BKD == 0) {
+  // v3 stages 16 B per lane, so every column of A must start 16-B aligned
+  if (n % BM == 0 && k % BKD == 0 && lda % 2 == 0) {
     constexpr size_t lds3 = 2 * BKD * (BM + BN) * 8;
     static bool attr3t = false;
     if (!attr3t) {
-      hipFuncSetAttribute((const void*)k_dgemm_nt_v3<true>,
+      hipFuncSetAttribute((const void*)k_dgemm_nt_v3<V3_SYRK>,
                           hipFuncAttributeMaxDynamicSharedMemorySize, lds3);
       attr3t = true;
     }
-    hipLaunchKernelGGL(k_dgemm_nt_v3<true>, dim3(ntiles), dim3(512), lds3,
-                       stream, n, n, k, A, lda, A, lda, C, ldc, 0);
+    hipLaunchKernelGGL(k_dgemm_nt_v3<V3_SYRK>, dim3(ntiles), dim3(512), lds3,
+                       stream, n, n, k, A, lda, A, lda, C, ldc, 0, 0);
     return;
   }
   hipLaunchKernelGGL(k_dgemm_nt_v2<true>, dim3(ntiles), dim3(512), lds,
                      stream, n, n, k, A, lda, A, lda, C, ldc, 0);
+}
+
+// X[m x n] = B[m x n] * W[n x n]^T, W lower triangular with stored zeros
+// above its diagonal: the TRSM-by-inverse product at half the flops of the
+// dense dgemm. Requires m % 128 == 0 and n % 128 == 0 (callers dispatch).
+static void launch_dtrmm_rlt_order(int m, int n, const double* B, int ldb,
+                                   const double* W, int ldw, double* X,
+                                   int ldx, hipStream_t stream, int order) {
+  PA_CHECK(m > 0 && n > 0 && m % BM == 0 && n % BN == 0,
+           "dtrmm_rlt needs full 128x128 blocks, got %d x %d", m, n);
+  PA_CHECK(ldb >= m && ldx >= m && ldw >= n);
+  constexpr size_t lds = 2 * BKD * (BM + BN) * 8;
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)k_dgemm_nt_v3<V3_TRMM>,
+                        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr = true;
+  }
+  const int nbx = m / BM, nby = n / BN;
+  const int grid =
+      order == TRMM_SNAKE ? 8 * ((nby + 7) / 8) * nbx : nbx * nby;
+  hipLaunchKernelGGL(k_dgemm_nt_v3<V3_TRMM>, dim3(grid), dim3(512), lds,
+                     stream, m, n, n, B, ldb, W, ldw, X, ldx, nbx, order);
+}
+
+void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
+                      int ldw, double* X, int ldx, hipStream_t stream) {
+  launch_dtrmm_rlt_order(m, n, B, ldb, W, ldw, X, ldx, stream, TRMM_SNAKE);
 }
 
 void gpu_gemm_hip(Task& t, GpuTaskCtx& g) {
@@ -473,6 +559,25 @@ void test_dgemm_nt_hip(int m, int n, int k, const double* A, int lda,
   PA_HIP_CHECK(hipFree(dC));
 }
 
+// X = B * W^T on device, host I/O. X is uploaded too, so a caller can show
+// that whatever the output buffer held is ignored (beta = 0).
+void test_dtrmm_rlt_hip(int m, int n, const double* B, int ldb,
+                        const double* W, int ldw, double* X, int ldx) {
+  double *dB, *dW, *dX;
+  PA_HIP_CHECK(hipMalloc(&dB, (size_t)ldb * n * 8));
+  PA_HIP_CHECK(hipMalloc(&dW, (size_t)ldw * n * 8));
+  PA_HIP_CHECK(hipMalloc(&dX, (size_t)ldx * n * 8));
+  PA_HIP_CHECK(hipMemcpy(dB, B, (size_t)ldb * n * 8, hipMemcpyHostToDevice));
+  PA_HIP_CHECK(hipMemcpy(dW, W, (size_t)ldw * n * 8, hipMemcpyHostToDevice));
+  PA_HIP_CHECK(hipMemcpy(dX, X, (size_t)ldx * n * 8, hipMemcpyHostToDevice));
+  launch_dtrmm_rlt(m, n, dB, ldb, dW, ldw, dX, ldx, 0);
+  PA_HIP_CHECK(hipGetLastError());
+  PA_HIP_CHECK(hipMemcpy(X, dX, (size_t)ldx * n * 8, hipMemcpyDeviceToHost));
+  PA_HIP_CHECK(hipFree(dB));
+  PA_HIP_CHECK(hipFree(dW));
+  PA_HIP_CHECK(hipFree(dX));
+}
+
 __global__ void k_bench_fill(double* p, size_t n, uint32_t seed) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -516,6 +621,37 @@ double bench_dgemm_hip(int m, int n, int k, int iters, int impl) {
   PA_HIP_CHECK(hipFree(dA));
   PA_HIP_CHECK(hipFree(dB));
   PA_HIP_CHECK(hipFree(dC));
+  return dt;
+}
+
+// Timed device-resident X = B * W^T loop for choosing the block order
+// (order: 0 snake, 1 descending, 2 ascending, 3 flat). W is lower
+// triangular with zeros above. Returns seconds.
+double bench_dtrmm_hip(int m, int n, int iters, int order) {
+  PA_CHECK(order >= TRMM_SNAKE && order <= TRMM_FLAT);
+  double *dB, *dW, *dX;
+  PA_HIP_CHECK(hipMalloc(&dB, (size_t)m * n * 8));
+  PA_HIP_CHECK(hipMalloc(&dW, (size_t)n * n * 8));
+  PA_HIP_CHECK(hipMalloc(&dX, (size_t)m * n * 8));
+  hipLaunchKernelGGL(k_bench_fill, dim3(2048), dim3(256), 0, 0, dB,
+                     (size_t)m * n, 11u);
+  hipLaunchKernelGGL(k_bench_fill, dim3(2048), dim3(256), 0, 0, dW,
+                     (size_t)n * n, 12u);
+  // zero the strictly-upper part of W, column by column
+  for (int c = 1; c < n; c++)
+    PA_HIP_CHECK(hipMemsetAsync(dW + (size_t)c * n, 0, (size_t)c * 8, 0));
+  auto run = [&] {
+    launch_dtrmm_rlt_order(m, n, dB, m, dW, n, dX, m, 0, order);
+  };
+  run();
+  PA_HIP_CHECK(hipDeviceSynchronize());
+  double t0 = now_s();
+  for (int i = 0; i < iters; i++) run();
+  PA_HIP_CHECK(hipDeviceSynchronize());
+  double dt = now_s() - t0;
+  PA_HIP_CHECK(hipFree(dB));
+  PA_HIP_CHECK(hipFree(dW));
+  PA_HIP_CHECK(hipFree(dX));
   return dt;
 }
 

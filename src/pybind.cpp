@@ -26,8 +26,11 @@ std::string rccl_get_unique_id();
 void rccl_set_unique_id(const std::string&);
 void test_dgemm_nt_hip(int, int, int, const double*, int, const double*, int,
                        double*, int);
+void test_dtrmm_rlt_hip(int, int, const double*, int, const double*, int,
+                        double*, int);
 void test_potf2_hip(double*, int);
 double bench_dgemm_hip(int, int, int, int, int);
+double bench_dtrmm_hip(int, int, int, int);
 double bench_dgemm_rocblas(int, int, int, int);
 double bench_gemm_bf16(int, int, int, int);
 double bench_qr_factor(int, int, int, int, int);
@@ -556,9 +559,25 @@ PYBIND11_MODULE(_core, m) {
     pa::test_dgemm_nt_hip(m, n, k, A.data(), m, B.data(), n,
                           C.mutable_data(), m);
   });
+  m.def("dtrmm_rlt_hip", [](py::array_t<double> B, py::array_t<double> W,
+                            py::array_t<double> X, int m, int n, int ldb,
+                            int ldw, int ldx) {
+    // X[m x n] = B[m x n] * W[n x n]^T; column-major buffers flattened 1-D
+    // with n columns of ldb / ldw / ldx doubles each
+    if (m <= 0 || n <= 0 || ldb < m || ldx < m || ldw < n ||
+        B.size() < (py::ssize_t)ldb * n || W.size() < (py::ssize_t)ldw * n ||
+        X.size() < (py::ssize_t)ldx * n)
+      throw std::invalid_argument("dtrmm_rlt_hip: buffer smaller than ld*n");
+    pa::test_dtrmm_rlt_hip(m, n, B.data(), ldb, W.data(), ldw,
+                           X.mutable_data(), ldx);
+  });
   m.def("potf2_hip", [](py::array_t<double> A, int n) {
     pa::test_potf2_hip(A.mutable_data(), n);
   });
+  // ms per launch of the triangular X = B W^T kernel under a block order
+  m.def("bench_dtrmm", [](int m, int n, int iters, int order) {
+    return pa::bench_dtrmm_hip(m, n, iters, order) / iters * 1e3;
+  }, py::call_guard<py::gil_scoped_release>());
   m.def("bench_dgemm", [](int m, int n, int k, int iters, std::string impl) {
     double dt = impl == "rocblas" ? pa::bench_dgemm_rocblas(m, n, k, iters)
                                   : pa::bench_dgemm_hip(m, n, k, iters,
