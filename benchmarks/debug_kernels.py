@@ -42,7 +42,7 @@ for n in [16, 64, 100, 128]:
 
 print("\n--- dgemm kernel throughput (TFLOP/s, device-resident) ---")
 for (m,n,k) in [(2048,2048,2048), (4096,4096,4096), (8192,8192,2048)]:
-    for impl in ["v2", "v1", "rocblas"]:
+    for impl in ["hip", "rocblas"]:
         tf = _core.bench_dgemm(m, n, k, 10, impl)
         print(f"{m}x{n}x{k} {impl}: {tf:.1f} TF/s")
 

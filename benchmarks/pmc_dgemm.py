@@ -12,5 +12,5 @@ if which == "bf16":
     from parsec_amd._core import bench_gemm_bf16
     print(f"bf16: {bench_gemm_bf16(n, n, n, 20):.0f} TF")
 else:
-    tf = bench_dgemm(n, n, n, iters, "rocblas" if which == "rocblas" else "v2")
+    tf = bench_dgemm(n, n, n, iters, "rocblas" if which == "rocblas" else "hip")
     print(f"{which}: {tf:.1f} TF")

@@ -15,6 +15,8 @@
 #include <rocsolver/rocsolver.h>
 
 #include "device_gpu.hpp"
+#include "gpu_blas.hpp"
+#include "kernels_hip.hpp"
 #include "profiling.hpp"
 
 namespace pa {
@@ -171,42 +173,12 @@ static void cpu_gemm(Task& t) {
   t.flows[2].data->written_on(false);
 }
 
-void launch_dsyrk_v2(int n, int k, const double* A, int lda, double* C,
-                     int ldc, hipStream_t stream);  // kernels_hip.cpp
-void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
-                      int ldw, double* X, int ldx,
-                      hipStream_t stream);  // kernels_hip.cpp
-
 // ------------------------------------------------------------------ GPU chores
-// One rocBLAS handle PER EXEC STREAM: rocBLAS/rocSOLVER keep device
-// workspace on the handle (e.g. dtrsm's invA), so concurrent kernels on
-// different streams must not share one. Hooks run on the manager thread
-// only, so a thread_local map is race-free.
-static rocblas_handle blas_handle(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_handle> handles;
-  rocblas_handle& h = handles[(void*)g.stream];
-  if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
-    rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
-    rocblas_set_stream(h, g.stream);
-  }
-  return h;
-}
-
-static rocblas_int* dev_info(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_int*> infos;
-  rocblas_int*& p = infos[(void*)g.stream];
-  if (!p) PA_HIP_CHECK(hipMalloc(&p, sizeof(rocblas_int)));
-  return p;
-}
-
-void launch_potf2(double* A, int n, int ld, hipStream_t stream);  // kernels_hip
-
 // Blocked tile POTRF: 128-wide LDS panel factorization (hand kernel) +
 // rocBLAS panel-TRSM + trailing SYRK, all in-order on the task's stream.
 // Critical-path op: measured ~3x faster than rocsolver_dpotrf at nb=2048.
 // The trailing update runs on the hand triangular MFMA kernel
-// (launch_dsyrk_v2: lower block set only, one launch per panel; glds path
+// (launch_dsyrk_ln: lower block set only, one launch per panel; glds path
 // when the trailing size is a multiple of 128, bounds-checked path
 // otherwise) instead of rocblas_dsyrk's k=128 decomposition into several
 // small Tensile + syrkx launches per panel. It also writes the upper half
@@ -232,7 +204,7 @@ static void gpu_potrf_blocked(Task& t, GpuTaskCtx& g) {
                              ld, Aij, ld) == rocblas_status_success);
       double* Att = A + (size_t)(j + jb) * ld + j + jb;
       if (syrk_hip) {
-        launch_dsyrk_v2(rest, jb, Aij, ld, Att, ld, g.stream);
+        launch_dsyrk_ln(rest, jb, Aij, ld, Att, ld, g.stream);
         continue;
       }
       PA_CHECK(rocblas_dsyrk(h, rocblas_fill_lower, rocblas_operation_none,
@@ -271,7 +243,7 @@ static void gpu_syrk(Task& t, GpuTaskCtx& g) {
   if (use_hip) {
     // hand MFMA kernel over the lower-triangular block set only: half the
     // FLOPs of the full-tile dgemm route.
-    launch_dsyrk_v2(a.n, a.k, (const double*)t.dev_ptr[0], a.ld,
+    launch_dsyrk_ln(a.n, a.k, (const double*)t.dev_ptr[0], a.ld,
                     (double*)t.dev_ptr[1], a.ld, g.stream);
     return;
   }
@@ -309,18 +281,6 @@ static void gpu_trtri(Task& t, GpuTaskCtx& g) {
 // step and broadcast like the diagonal tile. By default the product runs on
 // the triangular-aware hand kernel (launch_dtrmm_rlt, half the flops);
 // PARSEC_MCA_chore_trsm_inv=rocblas keeps the dense dgemm.
-static void* stream_scratch(GpuTaskCtx& g, size_t bytes) {
-  static thread_local std::map<void*, std::pair<void*, size_t>> bufs;
-  auto& e = bufs[(void*)g.stream];
-  if (e.second < bytes) {
-    // old buffer may still be in use by earlier kernels on this stream
-    if (e.first) g.deferred_frees->emplace_back(e.first, e.second);
-    e.first = g.engine->dev_alloc(bytes);
-    e.second = bytes;
-  }
-  return e.first;
-}
-
 static void gpu_trsm_inv(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   Data* bd = t.flows[1].data;
@@ -353,8 +313,6 @@ static void gpu_trsm_inv(Task& t, GpuTaskCtx& g) {
   }
   t.dev_ptr[1] = X;
 }
-
-void gpu_gemm_hip(Task& t, GpuTaskCtx& g);  // kernels_hip.cpp
 
 static void gpu_gemm(Task& t, GpuTaskCtx& g) {
   static const bool use_hip = param_str("chore_gemm", "rocblas") == "hip";

@@ -9,30 +9,19 @@
 // pattern) + rocBLAS trsm/gemm. CPU chores: reference loops for the
 // no-GPU test path.
 #include <cstring>
-#include <map>
 
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
 #include "device_gpu.hpp"
+#include "gpu_blas.hpp"
 #include "kernels.hpp"
 #include "profiling.hpp"
 
 namespace pa {
 
 namespace {
-
-rocblas_handle lu_handle(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_handle> handles;
-  rocblas_handle& h = handles[(void*)g.stream];
-  if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
-    rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
-    rocblas_set_stream(h, g.stream);
-  }
-  return h;
-}
 
 // ---- CPU reference chores (column-major, ld = tile rows) ----
 void cpu_getrf(Task& t) {
@@ -179,17 +168,10 @@ void cpu_trsm_l_inv(Task& t) {
 }
 
 // ---- GPU chores ----
-rocblas_int* lu_dev_info(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_int*> infos;
-  rocblas_int*& p = infos[(void*)g.stream];
-  if (!p) PA_HIP_CHECK(hipMalloc(&p, sizeof(rocblas_int)));
-  return p;
-}
-
 void gpu_getrf(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
-  rocblas_int* dinfo = lu_dev_info(g);
-  PA_CHECK(rocsolver_dgetrf_npvt(lu_handle(g), a.n, a.n,
+  rocblas_int* dinfo = dev_info(g);
+  PA_CHECK(rocsolver_dgetrf_npvt(blas_handle(g), a.n, a.n,
                                  (double*)t.dev_ptr[0], a.ld,
                                  dinfo) == rocblas_status_success);
   // Blocking chore (worker thread): read the info scalar back so a
@@ -205,7 +187,7 @@ void gpu_getrf(Task& t, GpuTaskCtx& g) {
 void gpu_trsm_l(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dtrsm(lu_handle(g), rocblas_side_left,
+  PA_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_left,
                          rocblas_fill_lower, rocblas_operation_none,
                          rocblas_diagonal_unit, a.m, a.n, &one,
                          (const double*)t.dev_ptr[0], a.ld,
@@ -216,7 +198,7 @@ void gpu_trsm_l(Task& t, GpuTaskCtx& g) {
 void gpu_trsm_u(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dtrsm(lu_handle(g), rocblas_side_right,
+  PA_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_right,
                          rocblas_fill_upper, rocblas_operation_none,
                          rocblas_diagonal_non_unit, a.m, a.n, &one,
                          (const double*)t.dev_ptr[0], a.ld,
@@ -227,7 +209,7 @@ void gpu_trsm_u(Task& t, GpuTaskCtx& g) {
 void gpu_gemm_nn(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double mone = -1.0, one = 1.0;
-  PA_CHECK(rocblas_dgemm(lu_handle(g), rocblas_operation_none,
+  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
                          rocblas_operation_none, a.m, a.n, a.k, &mone,
                          (const double*)t.dev_ptr[0], a.ld,
                          (const double*)t.dev_ptr[1], a.ld, &one,
@@ -240,7 +222,7 @@ void gpu_lu_trtri(Task& t, GpuTaskCtx& g) {
   Data* wd = t.flows[1].data;
   double* W = (double*)t.dev_ptr[1];
   PA_HIP_CHECK(hipMemsetAsync(W, 0, wd->bytes, g.stream));
-  rocblas_handle h = lu_handle(g);
+  rocblas_handle h = blas_handle(g);
   PA_CHECK(rocblas_dtrtri(h, rocblas_fill_upper, rocblas_diagonal_non_unit,
                           a.n, (const double*)t.dev_ptr[0], a.ld, W,
                           a.n) == rocblas_status_success);
@@ -257,7 +239,7 @@ void lu_swap_gemm(Task& t, GpuTaskCtx& g, const double* A0, int lda,
   Data* bd = t.flows[1].data;
   double* X = (double*)g.engine->dev_alloc(bd->bytes);
   const double one = 1.0, zero = 0.0;
-  PA_CHECK(rocblas_dgemm(lu_handle(g), rocblas_operation_none,
+  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
                          rocblas_operation_none, m, n, k, &one, A0, lda, B0,
                          ldb, &zero, X, m) == rocblas_status_success);
   {

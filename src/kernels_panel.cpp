@@ -13,7 +13,6 @@
 // variant exposes more parallelism. bench.py picks per world size
 // (--algo auto).
 #include <cmath>
-#include <map>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -21,12 +20,12 @@
 #include <rocsolver/rocsolver.h>
 
 #include "device_gpu.hpp"
+#include "gpu_blas.hpp"
 #include "kernels.hpp"
+#include "kernels_hip.hpp"
 #include "profiling.hpp"
 
 namespace pa {
-
-void launch_potf2(double* A, int n, int ld, hipStream_t stream);
 
 // ------------------------------------------------------------------ fill
 __global__ void k_panel_fill(double* p, int64_t rows, int cols, int64_t ld,
@@ -75,18 +74,6 @@ static void cpu_panel_fill(Task& t) {
 }
 
 // ------------------------------------------------------------------ chores
-namespace {
-rocblas_handle pan_handle(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_handle> handles;
-  rocblas_handle& h = handles[(void*)g.stream];
-  if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
-    rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
-    rocblas_set_stream(h, g.stream);
-  }
-  return h;
-}
-}  // namespace
 
 // PANEL(k): potrf of the nb x nb diagonal block (128-wide hand MFMA potf2
 // pipeline + rocBLAS trsm/syrk, as the tile chore) then the big TRSM of
@@ -96,7 +83,7 @@ static void gpu_panel_factor(Task& t, GpuTaskCtx& g) {
   const int64_t ld = a.ld;
   const int nb = a.n;
   double* diag = (double*)t.dev_ptr[0] + a.i0;  // rows k*nb.., col 0
-  rocblas_handle h = pan_handle(g);
+  rocblas_handle h = blas_handle(g);
   const double one = 1.0, mone = -1.0;
   for (int j = 0; j < nb; j += 128) {
     int jb = std::min(128, nb - j);
@@ -171,7 +158,7 @@ static void gpu_panel_update(Task& t, GpuTaskCtx& g) {
   const double* A1 = (const double*)t.dev_ptr[0] + a.i0;  // rows n*nb..
   const double* A2 = (const double*)t.dev_ptr[0] + a.i0;  // top nb_n rows
   double* C = (double*)t.dev_ptr[1] + a.i0;
-  PA_CHECK(rocblas_dgemm(pan_handle(g), rocblas_operation_none,
+  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
                          rocblas_operation_transpose, (int)a.m, a.n, a.k,
                          &mone, A1, (int)ld, A2, (int)ld, &one, C,
                          (int)ld) == rocblas_status_success);

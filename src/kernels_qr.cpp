@@ -23,6 +23,7 @@
 #include <rocsolver/rocsolver.h>
 
 #include "device_gpu.hpp"
+#include "gpu_blas.hpp"
 #include "kernels.hpp"
 #include "profiling.hpp"
 
@@ -211,17 +212,6 @@ __global__ void k_qr_fill(double* p, size_t n, uint32_t seed) {
     h ^= h >> 32;
     p[i] = (double)(h & 0xFFFFFF) / (double)0x1000000 - 0.5;
   }
-}
-
-rocblas_handle qr_handle(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_handle> handles;
-  rocblas_handle& h = handles[(void*)g.stream];
-  if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
-    rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
-    rocblas_set_stream(h, g.stream);
-  }
-  return h;
 }
 
 double* qr_scratch(GpuTaskCtx& g, int slot, size_t bytes) {
@@ -1044,7 +1034,7 @@ __global__ void __launch_bounds__(128) k_larft_diag(const double* G, int ldg,
 // diagonal band, capping active rows at 128 + (m - ts_split).
 static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
                            double* T, int ldt, int slot0, int ts_split = 0) {
-  rocblas_handle h = qr_handle(g);
+  rocblas_handle h = blas_handle(g);
   double* tau = qr_scratch(g, slot0, (size_t)k * 8);
   double* T16s = qr_scratch(g, slot0 + 9, (size_t)8 * 256 * 8);
   int* cnt = (int*)qr_scratch(g, slot0 + 10, 256);
@@ -1159,7 +1149,7 @@ static void gpu_geqrt(Task& t, GpuTaskCtx& g) {
     return;
   }
   double* tau = qr_scratch(g, 0, (size_t)a.n * 8);
-  rocblas_handle h = qr_handle(g);
+  rocblas_handle h = blas_handle(g);
   PA_HIP_CHECK(hipMemsetAsync(T, 0, t.flows[1].data->bytes, g.stream));
   PA_CHECK(rocsolver_dgeqrf(h, a.n, a.n, A, a.ld, tau) ==
            rocblas_status_success);
@@ -1187,7 +1177,7 @@ __global__ void k_unitlow(double* V, const double* A, int m, int k, int lda,
 static void larfb_gemm(GpuTaskCtx& g, int m, int n, int k, const double* A,
                        int lda, const double* T, int ldt, double* C, int ldc,
                        int scratch_slot) {
-  rocblas_handle h = qr_handle(g);
+  rocblas_handle h = blas_handle(g);
   double* V = qr_scratch(g, scratch_slot, (size_t)m * k * 8);
   double* W = qr_scratch(g, scratch_slot + 1, (size_t)k * n * 8);
   hipLaunchKernelGGL(k_unitlow, grid1d(m * k), dim3(256), 0, g.stream, V, A,
@@ -1222,7 +1212,7 @@ static void gpu_tsqrt(Task& t, GpuTaskCtx& g) {
   double* Amk = (double*)t.dev_ptr[1];
   double* V2 = (double*)t.dev_ptr[2];
   double* T1 = (double*)t.dev_ptr[3];
-  rocblas_handle h = qr_handle(g);
+  rocblas_handle h = blas_handle(g);
   hipLaunchKernelGGL(k_stack_triu, grid1d(nb * nb), dim3(256), 0, g.stream,
                      V2, Akk, Amk, nb, ld, a.k);
   static const bool use_rocsolver =
@@ -1467,7 +1457,7 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
                            (int)param_int("qr_lookahead", 1), dbg);
       }
     } else {
-      PA_CHECK(rocsolver_dgeqrf(qr_handle(g), m, k, dA, m, tau) ==
+      PA_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA, m, tau) ==
                rocblas_status_success);
     }
   };

@@ -28,23 +28,13 @@
 #include <rocblas/rocblas.h>
 
 #include "device_gpu.hpp"
+#include "gpu_blas.hpp"
 #include "kernels.hpp"
 #include "profiling.hpp"
 
 namespace pa {
 
 namespace {
-
-rocblas_handle bc_handle(GpuTaskCtx& g) {
-  static thread_local std::map<void*, rocblas_handle> handles;
-  rocblas_handle& h = handles[(void*)g.stream];
-  if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
-    rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
-    rocblas_set_stream(h, g.stream);
-  }
-  return h;
-}
 
 // ---- G += A^T B (TN accumulate; also the syrk step with B = A) ----
 void cpu_gemm_tn_acc(Task& t) {
@@ -66,7 +56,7 @@ void cpu_gemm_tn_acc(Task& t) {
 void gpu_gemm_tn_acc(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dgemm(bc_handle(g), rocblas_operation_transpose,
+  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_transpose,
                          rocblas_operation_none, a.n, a.n, a.m, &one,
                          (const double*)t.dev_ptr[0], a.ld,
                          (const double*)t.dev_ptr[1], a.ld, &one,
@@ -149,7 +139,7 @@ void cpu_gemm_nn_sub(Task& t) {
 void gpu_gemm_nn_sub(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double mone = -1.0, one = 1.0;
-  PA_CHECK(rocblas_dgemm(bc_handle(g), rocblas_operation_none,
+  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
                          rocblas_operation_none, a.m, a.n, a.k, &mone,
                          (const double*)t.dev_ptr[0], a.ld,
                          (const double*)t.dev_ptr[1], a.k, &one,

@@ -17,6 +17,7 @@
 #include "dtd.hpp"
 #include "gpu_graph.hpp"
 #include "kernels.hpp"
+#include "kernels_hip.hpp"
 #include "pins.hpp"
 #include "profiling.hpp"
 #include "runtime.hpp"
@@ -24,13 +25,6 @@
 namespace pa {
 std::string rccl_get_unique_id();
 void rccl_set_unique_id(const std::string&);
-void test_dgemm_nt_hip(int, int, int, const double*, int, const double*, int,
-                       double*, int);
-void test_dtrmm_rlt_hip(int, int, const double*, int, const double*, int,
-                        double*, int);
-void test_potf2_hip(double*, int);
-double bench_dgemm_hip(int, int, int, int, int);
-double bench_dtrmm_hip(int, int, int, int);
 double bench_dgemm_rocblas(int, int, int, int);
 double bench_gemm_bf16(int, int, int, int);
 double bench_qr_factor(int, int, int, int, int);
@@ -554,10 +548,28 @@ PYBIND11_MODULE(_core, m) {
   });
   // Standalone kernel harnesses for GPU numerics tests/debugging.
   m.def("dgemm_nt_hip", [](py::array_t<double> A, py::array_t<double> B,
-                           py::array_t<double> C, int m, int n, int k) {
-    // arrays are column-major buffers flattened 1-D, ld == rows
-    pa::test_dgemm_nt_hip(m, n, k, A.data(), m, B.data(), n,
-                          C.mutable_data(), m);
+                           py::array_t<double> C, int m, int n, int k, int lda,
+                           int ldb, int ldc) {
+    // C[m x n] -= A[m x k] * B[n x k]^T; column-major buffers flattened 1-D
+    // with k / k / n columns of lda / ldb / ldc doubles each (0: the rows)
+    if (lda == 0) lda = m;
+    if (ldb == 0) ldb = n;
+    if (ldc == 0) ldc = m;
+    if (m <= 0 || n <= 0 || k <= 0 || lda < m || ldb < n || ldc < m ||
+        A.size() < (py::ssize_t)lda * k || B.size() < (py::ssize_t)ldb * k ||
+        C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("dgemm_nt_hip: buffer smaller than ld*cols");
+    pa::test_dgemm_nt_hip(m, n, k, A.data(), lda, B.data(), ldb,
+                          C.mutable_data(), ldc);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+  m.def("dsyrk_ln_hip", [](py::array_t<double> A, py::array_t<double> C, int n,
+                           int k, int lda, int ldc) {
+    // C[n x n](lower blocks) -= A[n x k] * A^T; buffers as above
+    if (n <= 0 || k <= 0 || lda < n || ldc < n ||
+        A.size() < (py::ssize_t)lda * k || C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("dsyrk_ln_hip: buffer smaller than ld*cols");
+    pa::test_dsyrk_ln_hip(n, k, A.data(), lda, C.mutable_data(), ldc);
   });
   m.def("dtrmm_rlt_hip", [](py::array_t<double> B, py::array_t<double> W,
                             py::array_t<double> X, int m, int n, int ldb,
@@ -574,14 +586,16 @@ PYBIND11_MODULE(_core, m) {
   m.def("potf2_hip", [](py::array_t<double> A, int n) {
     pa::test_potf2_hip(A.mutable_data(), n);
   });
-  // ms per launch of the triangular X = B W^T kernel under a block order
-  m.def("bench_dtrmm", [](int m, int n, int iters, int order) {
-    return pa::bench_dtrmm_hip(m, n, iters, order) / iters * 1e3;
+  // ms per launch of the triangular X = B W^T kernel
+  m.def("bench_dtrmm", [](int m, int n, int iters) {
+    return pa::bench_dtrmm_hip(m, n, iters) / iters * 1e3;
   }, py::call_guard<py::gil_scoped_release>());
+  // impl: "hip" (the hand kernel; "v2" is its old name) or "rocblas"
   m.def("bench_dgemm", [](int m, int n, int k, int iters, std::string impl) {
+    if (impl != "hip" && impl != "v2" && impl != "rocblas")
+      throw std::invalid_argument("bench_dgemm: impl is \"hip\" or \"rocblas\"");
     double dt = impl == "rocblas" ? pa::bench_dgemm_rocblas(m, n, k, iters)
-                                  : pa::bench_dgemm_hip(m, n, k, iters,
-                                                        impl == "v1" ? 1 : 0);
+                                  : pa::bench_dgemm_hip(m, n, k, iters);
     return 2.0 * m * n * k * iters / dt / 1e12;  // TFLOP/s
   }, py::call_guard<py::gil_scoped_release>());
   // PCIe/xGMI link probe (reference tools/gpu/testbandwidth analog):
