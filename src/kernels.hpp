@@ -69,6 +69,14 @@ void insert_advise_prefetch(Dtd& tp, Data* d);
 // Cholesky solve / factor+solve (dplasma dpotrs/dposv analogs).
 void insert_potrs(Dtd& tp, TiledMatrix& A, TiledMatrix& B);
 void insert_posv(Dtd& tp, TiledMatrix& A, TiledMatrix& B);
+// SPD inverse, in place on the lower tiles (dplasma dtrtri/dlauum/dpotri/
+// dpoinv analogs): trtri turns L into W = L^-1, lauum turns W into the
+// lower tiles of W^T W, potri = trtri + lauum on a factor from insert_potrf,
+// poinv = potrf + potri in one taskpool.
+void insert_trtri(Dtd& tp, TiledMatrix& A);
+void insert_lauum(Dtd& tp, TiledMatrix& A);
+void insert_potri(Dtd& tp, TiledMatrix& A);
+void insert_poinv(Dtd& tp, TiledMatrix& A);
 // LU solve / factor+solve, no pivoting (dgetrs/dgesv nopiv analogs).
 void insert_getrs_nopiv(Dtd& tp, TiledMatrix& A, TiledMatrix& B);
 void insert_gesv_nopiv(Dtd& tp, TiledMatrix& A, TiledMatrix& B);

@@ -33,6 +33,9 @@
 //               its flops on W's stored zeros (chore_trsm_inv=hip|rocblas)
 //  - k_dgemm_nt_v2<TRI>, the bounds-checked kernel for every other GEMM and
 //    SYRK shape: register-staged, zero-filled past the edges.
+//  - k_dgemm_tn<KIND>, the bounds-checked kernel for C (+)= A^T B with
+//    triangular kinds: the LAUUM phase of the SPD inverse
+//    (chore_lauum=hip|rocblas, chore_gemm_tn=hip|rocblas).
 //  - k_potf2_mfma, the in-LDS Cholesky of one <=128 diagonal block.
 #include "kernels_hip.hpp"
 
@@ -262,6 +265,85 @@ __global__ void k_dgemm_nt_v3(int m, int n, int k, const double* __restrict__ A,
           /*checked=*/false, /*store=*/KIND == V3_TRMM);
 }
 
+// ------------------------------------------------------------------ tn
+// C[m x n] (+)= A[k x m]^T B[k x n]: both operands are contiguous along K,
+// the layout of the second half of the SPD inverse (A^-1 = W^T W with
+// W = L^-1 lower). The v2 structure with another staging step: each thread
+// reads along K (16 consecutive lanes cover one 128 B run of a column) and
+// writes transposed into the same [k][129] LDS image, zero-filled outside
+// m, n and k. Four kinds:
+//   TN_GEMM   C += A^T B on the full grid
+//   TN_SYRK   C += A^T A on the lower block set (B = A)
+//   TN_TRMM   X = W^T B, W (m x m, k == m) lower triangular: element (p, i)
+//             of W counts as 0 where p < i, so block row bx starts its K loop
+//             at its diagonal block; X is stored, never read
+//   TN_LAUUM  X = W^T W on the lower block set (m == n == k), both operands
+//             masked the same way
+// The mask is applied while staging, so whatever is stored above W's
+// diagonal (a diagonal tile carries junk there) never reaches an
+// accumulator and the MFMA loop stays branch-free. write_c subtracts, so
+// the accumulating kinds stage -A.
+enum { TN_GEMM = 0, TN_SYRK = 1, TN_TRMM = 2, TN_LAUUM = 3 };
+
+template <int KIND>
+__launch_bounds__(512)
+__global__ void k_dgemm_tn(int m, int n, int k, const double* __restrict__ A,
+                           int lda, const double* __restrict__ B, int ldb,
+                           double* __restrict__ C, int ldc, int nbx) {
+  constexpr bool TRI = KIND == TN_SYRK || KIND == TN_LAUUM;
+  constexpr bool STORE = KIND == TN_TRMM || KIND == TN_LAUUM;
+  constexpr bool MASK_B = KIND == TN_LAUUM;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LDT = 129;
+  double* As = (double*)smem;                  // [2][BKD][LDT]
+  double* Bs = As + 2 * BKD * LDT;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  int bx, by;
+  block_decode(TRI, nbx, bx, by);
+  const int bm0 = bx * BM, bn0 = by * BN;
+  const int ksub = lane >> 4, r16 = lane & 15;
+  // rows of W^T before its diagonal block are all masked
+  const int kbeg = STORE ? bm0 : 0;
+
+  f64x4 acc[2][4] = {};
+
+  auto stage = [&](int buf, int k0) {
+    double* as = As + buf * BKD * LDT;
+    double* bs = Bs + buf * BKD * LDT;
+#pragma unroll
+    for (int x = 0; x < BM * BKD; x += 512) {
+      int xi = x + tid;
+      int kk = xi & (BKD - 1), i = xi / BKD;
+      int gi = bm0 + i, gk = k0 + kk;
+      bool in = gi < m && gk < k && !(STORE && gk < gi);
+      double v = in ? A[(size_t)gi * lda + gk] : 0.0;
+      as[kk * LDT + i] = STORE ? v : -v;
+    }
+#pragma unroll
+    for (int x = 0; x < BN * BKD; x += 512) {
+      int xi = x + tid;
+      int kk = xi & (BKD - 1), j = xi / BKD;
+      int gj = bn0 + j, gk = k0 + kk;
+      bool in = gj < n && gk < k && !(MASK_B && gk < gj);
+      bs[kk * LDT + j] = in ? B[(size_t)gj * ldb + gk] : 0.0;
+    }
+  };
+
+  stage(0, kbeg);
+  __syncthreads();
+  const int ntiles = (k - kbeg + BKD - 1) / BKD;
+  for (int t = 0; t < ntiles; t++) {
+    if (t + 1 < ntiles) stage((t + 1) & 1, kbeg + (t + 1) * BKD);
+    mfma_ktile(acc, As + ((t & 1) * BKD + ksub) * LDT + wr * 32 + r16,
+               Bs + ((t & 1) * BKD + ksub) * LDT + wc * 64 + r16, LDT);
+    __syncthreads();
+  }
+  write_c(acc, C, ldc, bm0 + wr * 32 + ksub, bn0 + wc * 64 + r16, m, n,
+          /*checked=*/true, /*store=*/STORE);
+}
+
 // ------------------------------------------------------------- launchers
 // Every kernel here asks for more dynamic LDS than a launch gets by
 // default: raise that kernel's limit once, then launch.
@@ -322,6 +404,44 @@ void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
   launch_lds<k_dgemm_nt_v3<V3_TRMM>>(8 * ((nby + 7) / 8) * nbx, 512, LDS_V3,
                                      stream, m, n, n, B, ldb, W, ldw, X, ldx,
                                      nbx);
+}
+
+void launch_dgemm_tn(int m, int n, int k, const double* A, int lda,
+                     const double* B, int ldb, double* C, int ldc,
+                     hipStream_t stream) {
+  PA_CHECK(m > 0 && n > 0 && k > 0 && lda >= k && ldb >= k && ldc >= m,
+           "dgemm_tn: bad shape %d x %d x %d, ld %d %d %d", m, n, k, lda, ldb,
+           ldc);
+  const int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
+  launch_lds<k_dgemm_tn<TN_GEMM>>(nbx * nby, 512, LDS_V2, stream, m, n, k, A,
+                                  lda, B, ldb, C, ldc, nbx);
+}
+
+void launch_dsyrk_lt(int n, int k, const double* A, int lda, double* C,
+                     int ldc, hipStream_t stream) {
+  PA_CHECK(n > 0 && k > 0 && lda >= k && ldc >= n,
+           "dsyrk_lt: bad shape %d x %d, ld %d %d", n, k, lda, ldc);
+  const int ntb = (n + BM - 1) / BM;
+  launch_lds<k_dgemm_tn<TN_SYRK>>(ntb * (ntb + 1) / 2, 512, LDS_V2, stream, n,
+                                  n, k, A, lda, A, lda, C, ldc, 0);
+}
+
+void launch_dtrmm_llt(int m, int n, const double* W, int ldw, const double* B,
+                      int ldb, double* X, int ldx, hipStream_t stream) {
+  PA_CHECK(m > 0 && n > 0 && ldw >= m && ldb >= m && ldx >= m,
+           "dtrmm_llt: bad shape %d x %d, ld %d %d %d", m, n, ldw, ldb, ldx);
+  const int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
+  launch_lds<k_dgemm_tn<TN_TRMM>>(nbx * nby, 512, LDS_V2, stream, m, n, m, W,
+                                  ldw, B, ldb, X, ldx, nbx);
+}
+
+void launch_dlauum_l(int n, const double* W, int ldw, double* X, int ldx,
+                     hipStream_t stream) {
+  PA_CHECK(n > 0 && ldw >= n && ldx >= n,
+           "dlauum_l: bad shape %d, ld %d %d", n, ldw, ldx);
+  const int ntb = (n + BM - 1) / BM;
+  launch_lds<k_dgemm_tn<TN_LAUUM>>(ntb * (ntb + 1) / 2, 512, LDS_V2, stream, n,
+                                   n, n, W, ldw, W, ldw, X, ldx, 0);
 }
 
 void gpu_gemm_hip(Task& t, GpuTaskCtx& g) {
@@ -492,6 +612,36 @@ void test_dtrmm_rlt_hip(int m, int n, const double* B, int ldb,
   dX.download(X);
 }
 
+void test_dgemm_tn_hip(int m, int n, int k, const double* A, int lda,
+                       const double* B, int ldb, double* C, int ldc) {
+  DevArray dA((size_t)lda * m, A), dB((size_t)ldb * n, B),
+      dC((size_t)ldc * n, C);
+  launch_dgemm_tn(m, n, k, dA.p, lda, dB.p, ldb, dC.p, ldc, 0);
+  dC.download(C);
+}
+
+void test_dsyrk_lt_hip(int n, int k, const double* A, int lda, double* C,
+                       int ldc) {
+  DevArray dA((size_t)lda * n, A), dC((size_t)ldc * n, C);
+  launch_dsyrk_lt(n, k, dA.p, lda, dC.p, ldc, 0);
+  dC.download(C);
+}
+
+// X is uploaded for the two storing kinds, as in test_dtrmm_rlt_hip.
+void test_dtrmm_llt_hip(int m, int n, const double* W, int ldw,
+                        const double* B, int ldb, double* X, int ldx) {
+  DevArray dW((size_t)ldw * m, W), dB((size_t)ldb * n, B),
+      dX((size_t)ldx * n, X);
+  launch_dtrmm_llt(m, n, dW.p, ldw, dB.p, ldb, dX.p, ldx, 0);
+  dX.download(X);
+}
+
+void test_dlauum_l_hip(int n, const double* W, int ldw, double* X, int ldx) {
+  DevArray dW((size_t)ldw * n, W), dX((size_t)ldx * n, X);
+  launch_dlauum_l(n, dW.p, ldw, dX.p, ldx, 0);
+  dX.download(X);
+}
+
 void test_potf2_hip(double* A, int n) {
   DevArray dA((size_t)n * n, A);
   launch_potf2(dA.p, n, n, 0);
@@ -506,6 +656,29 @@ double bench_dgemm_hip(int m, int n, int k, int iters) {
   bench_fill(dC, 13);
   return time_launches(iters, [&] {
     launch_dgemm_nt(m, n, k, dA.p, m, dB.p, n, dC.p, m, 0);
+  });
+}
+
+// kind: TN_GEMM (m, n, k), TN_SYRK (n, k), TN_TRMM (m, n) or TN_LAUUM (n).
+// What W holds above its diagonal is masked, so every operand is random.
+double bench_dgemm_tn_hip(int kind, int m, int n, int k, int iters) {
+  PA_CHECK(kind >= TN_GEMM && kind <= TN_LAUUM, "bench_dgemm_tn: kind %d",
+           kind);
+  if (kind == TN_SYRK || kind == TN_LAUUM) m = n;
+  if (kind == TN_TRMM || kind == TN_LAUUM) k = m;
+  DevArray dA((size_t)k * m), dB((size_t)k * n), dC((size_t)m * n);
+  bench_fill(dA, 11);
+  bench_fill(dB, 12);
+  bench_fill(dC, 13);
+  return time_launches(iters, [&] {
+    switch (kind) {
+      case TN_GEMM:
+        launch_dgemm_tn(m, n, k, dA.p, k, dB.p, k, dC.p, m, 0);
+        break;
+      case TN_SYRK: launch_dsyrk_lt(n, k, dA.p, k, dC.p, n, 0); break;
+      case TN_TRMM: launch_dtrmm_llt(m, n, dA.p, m, dB.p, m, dC.p, m, 0); break;
+      default: launch_dlauum_l(n, dA.p, n, dC.p, n, 0);
+    }
   });
 }
 

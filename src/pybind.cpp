@@ -26,6 +26,7 @@ namespace pa {
 std::string rccl_get_unique_id();
 void rccl_set_unique_id(const std::string&);
 double bench_dgemm_rocblas(int, int, int, int);
+double bench_tn_rocblas(int, int, int, int, int);
 double bench_gemm_bf16(int, int, int, int);
 double bench_qr_factor(int, int, int, int, int);
 void test_gemm_bf16_hip(int, int, int, const uint16_t*, const uint16_t*,
@@ -452,6 +453,14 @@ PYBIND11_MODULE(_core, m) {
         py::arg("B"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_posv", &insert_posv, py::arg("tp"), py::arg("A"),
         py::arg("B"), py::call_guard<py::gil_scoped_release>());
+  m.def("insert_trtri", &insert_trtri, py::arg("tp"), py::arg("A"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("insert_lauum", &insert_lauum, py::arg("tp"), py::arg("A"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("insert_potri", &insert_potri, py::arg("tp"), py::arg("A"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("insert_poinv", &insert_poinv, py::arg("tp"), py::arg("A"),
+        py::call_guard<py::gil_scoped_release>());
   m.def("insert_getrs_nopiv", &insert_getrs_nopiv, py::arg("tp"),
         py::arg("A"), py::arg("B"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_gesv_nopiv", &insert_gesv_nopiv, py::arg("tp"),
@@ -583,6 +592,69 @@ PYBIND11_MODULE(_core, m) {
     pa::test_dtrmm_rlt_hip(m, n, B.data(), ldb, W.data(), ldw,
                            X.mutable_data(), ldx);
   });
+  // The TN family: operands are k x m / k x n, contiguous along K.
+  m.def("dgemm_tn_hip", [](py::array_t<double> A, py::array_t<double> B,
+                           py::array_t<double> C, int m, int n, int k, int lda,
+                           int ldb, int ldc) {
+    // C[m x n] += A[k x m]^T * B[k x n]; column-major buffers flattened 1-D
+    // with m / n / n columns of lda / ldb / ldc doubles each (0: the rows)
+    if (lda == 0) lda = k;
+    if (ldb == 0) ldb = k;
+    if (ldc == 0) ldc = m;
+    if (m <= 0 || n <= 0 || k <= 0 || lda < k || ldb < k || ldc < m ||
+        A.size() < (py::ssize_t)lda * m || B.size() < (py::ssize_t)ldb * n ||
+        C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("dgemm_tn_hip: buffer smaller than ld*cols");
+    pa::test_dgemm_tn_hip(m, n, k, A.data(), lda, B.data(), ldb,
+                          C.mutable_data(), ldc);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+  m.def("dsyrk_lt_hip", [](py::array_t<double> A, py::array_t<double> C, int n,
+                           int k, int lda, int ldc) {
+    // C[n x n](lower blocks) += A[k x n]^T * A
+    if (n <= 0 || k <= 0 || lda < k || ldc < n ||
+        A.size() < (py::ssize_t)lda * n || C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("dsyrk_lt_hip: buffer smaller than ld*cols");
+    pa::test_dsyrk_lt_hip(n, k, A.data(), lda, C.mutable_data(), ldc);
+  });
+  m.def("dtrmm_llt_hip", [](py::array_t<double> W, py::array_t<double> B,
+                            py::array_t<double> X, int m, int n, int ldw,
+                            int ldb, int ldx) {
+    // X[m x n] = W[m x m]^T * B[m x n], W lower (its strict upper is ignored)
+    if (m <= 0 || n <= 0 || ldw < m || ldb < m || ldx < m ||
+        W.size() < (py::ssize_t)ldw * m || B.size() < (py::ssize_t)ldb * n ||
+        X.size() < (py::ssize_t)ldx * n)
+      throw std::invalid_argument("dtrmm_llt_hip: buffer smaller than ld*cols");
+    pa::test_dtrmm_llt_hip(m, n, W.data(), ldw, B.data(), ldb,
+                           X.mutable_data(), ldx);
+  });
+  m.def("dlauum_l_hip", [](py::array_t<double> W, py::array_t<double> X, int n,
+                           int ldw, int ldx) {
+    // X[n x n](lower blocks) = W^T * W, W lower (its strict upper is ignored)
+    if (n <= 0 || ldw < n || ldx < n || W.size() < (py::ssize_t)ldw * n ||
+        X.size() < (py::ssize_t)ldx * n)
+      throw std::invalid_argument("dlauum_l_hip: buffer smaller than ld*n");
+    pa::test_dlauum_l_hip(n, W.data(), ldw, X.mutable_data(), ldx);
+  });
+  // ms per launch of one TN kind ("gemm" m n k, "syrk" n k, "trmm" m n,
+  // "lauum" n; unused sizes are ignored); impl "hip" is the hand kernel,
+  // "rocblas" the library route of the same tile operation
+  m.def("bench_dgemm_tn", [](std::string kind, int m, int n, int k, int iters,
+                             std::string impl) {
+    static const std::map<std::string, int> kinds = {
+        {"gemm", 0}, {"syrk", 1}, {"trmm", 2}, {"lauum", 3}};
+    auto it = kinds.find(kind);
+    if (it == kinds.end() || (impl != "hip" && impl != "rocblas") ||
+        iters <= 0)
+      throw std::invalid_argument(
+          "bench_dgemm_tn: kind gemm|syrk|trmm|lauum, impl hip|rocblas");
+    double dt = impl == "hip"
+                    ? pa::bench_dgemm_tn_hip(it->second, m, n, k, iters)
+                    : pa::bench_tn_rocblas(it->second, m, n, k, iters);
+    return dt / iters * 1e3;
+  }, py::arg("kind"), py::arg("m"), py::arg("n"), py::arg("k"),
+     py::arg("iters"), py::arg("impl") = "hip",
+     py::call_guard<py::gil_scoped_release>());
   m.def("potf2_hip", [](py::array_t<double> A, int n) {
     pa::test_potf2_hip(A.mutable_data(), n);
   });
