@@ -90,4 +90,11 @@ void insert_stencil_1d(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_panel_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_potrf_panel(Dtd& tp, TiledMatrix& A);
 
+// Test entry point of the QR panel factorization (kernels_qr.cpp): host
+// buffers in, factored A and the k x k T out. impl: 0 hand kernels, 1
+// rocSOLVER route, 2 CPU kernels.
+void test_qr_factor_hip(double* A, size_t a_elems, int m, int k, int lda,
+                        int ts_split, int impl, int wgs, int poolA,
+                        const std::string& apply, int lookahead, double* T);
+
 }  // namespace pa

@@ -378,6 +378,9 @@ namespace {
 constexpr int QR_LDS_DOUBLES = 18432;  // 144 KiB panel + ~8 KiB reduction
 constexpr int QR_MAX_ROWS_W16 = 1152;
 constexpr int QR_MAX_ROWS_W8 = 2304;
+// T16s holds one 16x16 block per sub-panel: a 128-column panel is 8
+// sub-panels at W=16 and 16 at W=8.
+constexpr int QR_MAX_SUBPANELS = 16;
 
 __device__ inline void qr_grid_barrier(int* cnt, int nwg, int bar_no) {
   __syncthreads();
@@ -884,7 +887,9 @@ __global__ void __launch_bounds__(1024) k_qr_panel_mw(
     // apply (I - V T V^T)^T to 4-column groups of my column set
     auto apply4 = [&](int cg[4], int nc) {
       const int ci = lane >> 4, l16 = lane & 15;  // unit = (q=wave, ci)
-      if (ci < nc) {
+      // wave >= w has no reflector: with W=8 its sp + wave * rows lies
+      // past the V image (past sp itself at 2304 rows)
+      if (ci < nc && wave < w) {
         const int gcol = pcol0 + cg[ci];
         const int cloc = c0 + wave;
         const double* v = sp + (size_t)wave * rows;
@@ -1026,6 +1031,40 @@ __global__ void __launch_bounds__(128) k_larft_diag(const double* G, int ldg,
     if (tid <= j) T[(size_t)(b0 + j) * ldt + b0 + tid] = Ts[j * 128 + tid];
 }
 
+// The tunables of the panel kernel. The chores and bench_qr_factor fill
+// them from the parameters of the same names; test_qr_factor_hip sets them
+// per call.
+struct QrPanelCfg {
+  int nwg = 48;             // qr_panel_wgs: workgroups per panel launch
+  int nA = 15;              // qr_panel_poolA: helpers on the panel columns
+  int amode = 1;            // qr_apply: 0 = valu helper apply, 1 = MFMA
+  bool apply_gemm = false;  // qr_apply=gemm: trailing columns by larfb dgemms
+  int look = 1;             // qr_lookahead
+  // kernel | valu | gemm; anything else is "kernel"
+  void set_apply(const std::string& kind) {
+    apply_gemm = kind == "gemm";
+    amode = kind == "valu" ? 0 : 1;
+  }
+  // WG 0 factors, so there is at least one helper, and pool A is never
+  // empty: nobody else applies a sub-panel to the panel's own columns.
+  void clamp() {
+    nwg = std::max(2, nwg);
+    nA = std::min(nwg - 1, std::max(1, nA));
+  }
+};
+
+static QrPanelCfg qr_cfg_from_params() {
+  // qr_apply is read once per process, the others on every call
+  static const std::string apply_kind = param_str("qr_apply", "kernel");
+  QrPanelCfg c;
+  c.nwg = (int)param_int("qr_panel_wgs", 48);
+  c.nA = (int)param_int("qr_panel_poolA", 15);
+  c.look = (int)param_int("qr_lookahead", 1);
+  c.set_apply(apply_kind);
+  c.clamp();
+  return c;
+}
+
 // Full tile/stacked-panel QR: factor 128-wide panels with the multi-WG
 // panel kernel (k_geqr2 single-WG fallback for oversized rows), apply to
 // the trailing columns with gemm-larfb, then build the full k x k T.
@@ -1033,13 +1072,13 @@ __global__ void __launch_bounds__(128) k_larft_diag(const double* G, int ldg,
 // the panel kernel then skips the structurally-zero block below R's
 // diagonal band, capping active rows at 128 + (m - ts_split).
 static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
-                           double* T, int ldt, int slot0, int ts_split = 0) {
+                           double* T, int ldt, int slot0, int ts_split,
+                           const QrPanelCfg& cfg) {
   rocblas_handle h = blas_handle(g);
   double* tau = qr_scratch(g, slot0, (size_t)k * 8);
-  double* T16s = qr_scratch(g, slot0 + 9, (size_t)8 * 256 * 8);
+  double* T16s = qr_scratch(g, slot0 + 9, (size_t)QR_MAX_SUBPANELS * 256 * 8);
   int* cnt = (int*)qr_scratch(g, slot0 + 10, 256);
-  const int nwg = std::max(2, (int)param_int("qr_panel_wgs", 48));
-  const int nA = std::min((int64_t)nwg - 1, param_int("qr_panel_poolA", 15));
+  const int nwg = cfg.nwg, nA = cfg.nA;
   const double one = 1.0, zero = 0.0, mone = -1.0;
   PA_HIP_CHECK(hipMemsetAsync(T, 0, (size_t)ldt * k * 8, g.stream));
   for (int p = 0; p < k; p += 128) {
@@ -1062,18 +1101,14 @@ static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
       // only; the trailing matrix goes through T128 + larfb dgemms at
       // Tensile rates (A/B: the in-kernel apply units are latency-bound,
       // profiles/qr_round2.md).
-      static const std::string apply_kind = param_str("qr_apply", "kernel");
-      static const bool apply_gemm = apply_kind == "gemm";
-      static const int amode = apply_kind == "valu" ? 0 : 1;
       int rest = k - p - pc;
-      int apply_cols = apply_gemm ? pc : k - p;
+      int apply_cols = cfg.apply_gemm ? pc : k - p;
       PA_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int), g.stream));
       hipLaunchKernelGGL(k_qr_panel_mw, dim3(nwg), dim3(1024), 0, g.stream,
                          A, ld, p, base0, len0, base1, len1, apply_cols, pc,
-                         W, tau + p, T16s, cnt, nwg, nA, amode,
-                         (int)param_int("qr_lookahead", 1),
+                         W, tau + p, T16s, cnt, nwg, nA, cfg.amode, cfg.look,
                          (unsigned long long*)nullptr);
-      if (apply_gemm && rest > 0) {
+      if (cfg.apply_gemm && rest > 0) {
         double* V = qr_scratch(g, slot0 + 1, (size_t)prows * 128 * 8);
         double* G = qr_scratch(g, slot0 + 2, (size_t)128 * 128 * 8);
         hipLaunchKernelGGL(k_unitlow, grid1d(prows * pc), dim3(256), 0,
@@ -1138,6 +1173,19 @@ static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
   }
 }
 
+// The chore_qr=rocsolver route: library dgeqrf, then dlarft for T (t_bytes
+// of it are cleared first).
+static void qr_factor_rocsolver(GpuTaskCtx& g, double* A, int m, int k,
+                                int ld, double* T, int ldt, size_t t_bytes) {
+  double* tau = qr_scratch(g, 0, (size_t)k * 8);
+  rocblas_handle h = blas_handle(g);
+  PA_HIP_CHECK(hipMemsetAsync(T, 0, t_bytes, g.stream));
+  PA_CHECK(rocsolver_dgeqrf(h, m, k, A, ld, tau) == rocblas_status_success);
+  PA_CHECK(rocsolver_dlarft(h, rocblas_forward_direction,
+                            rocblas_column_wise, m, k, A, ld, tau, T,
+                            ldt) == rocblas_status_success);
+}
+
 static void gpu_geqrt(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   double* A = (double*)t.dev_ptr[0];
@@ -1145,17 +1193,10 @@ static void gpu_geqrt(Task& t, GpuTaskCtx& g) {
   static const bool use_rocsolver =
       param_str("chore_qr", "hand") == "rocsolver";
   if (!use_rocsolver) {
-    qr_factor_hand(g, A, a.n, a.n, a.ld, T, a.ld, 0);
+    qr_factor_hand(g, A, a.n, a.n, a.ld, T, a.ld, 0, 0, qr_cfg_from_params());
     return;
   }
-  double* tau = qr_scratch(g, 0, (size_t)a.n * 8);
-  rocblas_handle h = blas_handle(g);
-  PA_HIP_CHECK(hipMemsetAsync(T, 0, t.flows[1].data->bytes, g.stream));
-  PA_CHECK(rocsolver_dgeqrf(h, a.n, a.n, A, a.ld, tau) ==
-           rocblas_status_success);
-  PA_CHECK(rocsolver_dlarft(h, rocblas_forward_direction,
-                            rocblas_column_wise, a.n, a.n, A, a.ld, tau, T,
-                            a.ld) == rocblas_status_success);
+  qr_factor_rocsolver(g, A, a.n, a.n, a.ld, T, a.ld, t.flows[1].data->bytes);
 }
 
 __global__ void k_unitlow(double* V, const double* A, int m, int k, int lda,
@@ -1212,21 +1253,16 @@ static void gpu_tsqrt(Task& t, GpuTaskCtx& g) {
   double* Amk = (double*)t.dev_ptr[1];
   double* V2 = (double*)t.dev_ptr[2];
   double* T1 = (double*)t.dev_ptr[3];
-  rocblas_handle h = blas_handle(g);
   hipLaunchKernelGGL(k_stack_triu, grid1d(nb * nb), dim3(256), 0, g.stream,
                      V2, Akk, Amk, nb, ld, a.k);
   static const bool use_rocsolver =
       param_str("chore_qr", "hand") == "rocsolver";
   if (!use_rocsolver) {
-    qr_factor_hand(g, V2, 2 * nb, nb, 2 * nb, T1, ld, 0, /*ts_split=*/nb);
+    qr_factor_hand(g, V2, 2 * nb, nb, 2 * nb, T1, ld, 0, /*ts_split=*/nb,
+                   qr_cfg_from_params());
   } else {
-    double* tau = qr_scratch(g, 0, (size_t)nb * 8);
-    PA_HIP_CHECK(hipMemsetAsync(T1, 0, t.flows[3].data->bytes, g.stream));
-    PA_CHECK(rocsolver_dgeqrf(h, 2 * nb, nb, V2, 2 * nb, tau) ==
-             rocblas_status_success);
-    PA_CHECK(rocsolver_dlarft(h, rocblas_forward_direction,
-                              rocblas_column_wise, 2 * nb, nb, V2, 2 * nb,
-                              tau, T1, ld) == rocblas_status_success);
+    qr_factor_rocsolver(g, V2, 2 * nb, nb, 2 * nb, T1, ld,
+                        t.flows[3].data->bytes);
   }
   hipLaunchKernelGGL(k_copy_triu, grid1d(nb * nb), dim3(256), 0, g.stream,
                      Akk, V2, nb, 2 * nb, ld);
@@ -1421,7 +1457,7 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
   std::vector<std::pair<void*, size_t>> defer;
   GpuTaskCtx g{s, 0, nullptr, &defer};
   double* tau = qr_scratch(g, 0, (size_t)k * 8);
-  double* T16s = qr_scratch(g, 9, (size_t)8 * 256 * 8);
+  double* T16s = qr_scratch(g, 9, (size_t)QR_MAX_SUBPANELS * 256 * 8);
   int* cnt = (int*)qr_scratch(g, 10, 256);
   unsigned long long* dbg = nullptr;
   if (mode == 5) {
@@ -1429,13 +1465,13 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
     PA_HIP_CHECK(hipMemset(dbg, 0, 16 * 8));
     mode = 1;
   }
-  const int nwg = std::max(2, (int)param_int("qr_panel_wgs", 48));
-  const int nA = std::min((int64_t)nwg - 1, param_int("qr_panel_poolA", 15));
+  const QrPanelCfg cfg = qr_cfg_from_params();
+  const int nwg = cfg.nwg, nA = cfg.nA;
   auto run = [&] {
     hipLaunchKernelGGL(k_qr_fill, dim3(2048), dim3(256), 0, s, dA,
                        (size_t)m * k, 7);
     if (mode == 0) {
-      qr_factor_hand(g, dA, m, k, m, dT, k, 0, ts_split);
+      qr_factor_hand(g, dA, m, k, m, dT, k, 0, ts_split, cfg);
     } else if (mode == 1 || mode >= 16) {
       for (int p = 0; p < k; p += 128) {
         int pc = std::min(128, k - p);
@@ -1452,9 +1488,8 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
         PA_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int), s));
         hipLaunchKernelGGL(k_qr_panel_mw, dim3(nwg), dim3(1024), 0, s, dA,
                            m, p, base0, len0, base1, len1, k - p, pc, W,
-                           tau + p, T16s, cnt, nwg, nA,
-                           param_str("qr_apply", "kernel") == "valu" ? 0 : 1,
-                           (int)param_int("qr_lookahead", 1), dbg);
+                           tau + p, T16s, cnt, nwg, nA, cfg.amode, cfg.look,
+                           dbg);
       }
     } else {
       PA_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA, m, tau) ==
@@ -1482,6 +1517,54 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
   PA_HIP_CHECK(hipFree(dA));
   PA_HIP_CHECK(hipFree(dT));
   return dt;
+}
+
+// One panel factorization from host buffers, for the tests: A (a_elems
+// doubles, column-major with leading dimension lda; what lies past column k
+// travels to the device and back untouched) is factored in place, T (k x k,
+// leading dimension k) receives the block reflector's triangular factor.
+// impl 0 = qr_factor_hand with the tunables the caller overrides (wgs,
+// poolA > 0; apply non-empty; lookahead >= 0), 1 = the rocSOLVER route of
+// chore_qr=rocsolver, 2 = the CPU chore's kernels (no GPU touched).
+void test_qr_factor_hip(double* A, size_t a_elems, int m, int k, int lda,
+                        int ts_split, int impl, int wgs, int poolA,
+                        const std::string& apply, int lookahead, double* T) {
+  if (impl == 2) {
+    std::vector<double> tau(k);
+    memset(T, 0, (size_t)k * k * 8);
+    cpu_geqrf_kern(m, k, A, lda, tau.data());
+    cpu_larft_kern(m, k, A, lda, tau.data(), T, k);
+    return;
+  }
+  // one stream per calling thread, kept: qr_scratch and blas_handle key
+  // their per-thread state on it
+  static thread_local hipStream_t s = nullptr;
+  if (!s) PA_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  double *dA, *dT;
+  PA_HIP_CHECK(hipMalloc(&dA, a_elems * 8));
+  PA_HIP_CHECK(hipMalloc(&dT, (size_t)k * k * 8));
+  PA_HIP_CHECK(hipMemcpy(dA, A, a_elems * 8, hipMemcpyHostToDevice));
+  std::vector<std::pair<void*, size_t>> defer;
+  GpuTaskCtx g{s, 0, nullptr, &defer};
+  if (impl == 0) {
+    QrPanelCfg cfg = qr_cfg_from_params();
+    if (wgs > 0) cfg.nwg = wgs;
+    if (poolA > 0) cfg.nA = poolA;
+    if (!apply.empty()) cfg.set_apply(apply);
+    if (lookahead >= 0) cfg.look = lookahead;
+    cfg.clamp();
+    qr_factor_hand(g, dA, m, k, lda, dT, k, 0, ts_split, cfg);
+  } else {
+    qr_factor_rocsolver(g, dA, m, k, lda, dT, k, (size_t)k * k * 8);
+  }
+  PA_HIP_CHECK(hipStreamSynchronize(s));
+  PA_HIP_CHECK(hipGetLastError());
+  PA_HIP_CHECK(hipMemcpy(A, dA, a_elems * 8, hipMemcpyDeviceToHost));
+  PA_HIP_CHECK(hipMemcpy(T, dT, (size_t)k * k * 8, hipMemcpyDeviceToHost));
+  // scratch that grew during this call was replaced, not freed
+  for (auto& d : defer) PA_HIP_CHECK(hipFree(d.first));
+  PA_HIP_CHECK(hipFree(dA));
+  PA_HIP_CHECK(hipFree(dT));
 }
 
 }  // namespace pa

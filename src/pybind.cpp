@@ -658,6 +658,50 @@ PYBIND11_MODULE(_core, m) {
   m.def("potf2_hip", [](py::array_t<double> A, int n) {
     pa::test_potf2_hip(A.mutable_data(), n);
   });
+  // QR of an m x k panel (m >= k) in place: R in the upper triangle, the
+  // unit-lower reflectors V below it; returns the k x k upper-triangular T
+  // of Q = I - V T V^T (tau on its diagonal). A is a column-major buffer
+  // flattened 1-D with at least k columns of lda doubles (0: m); columns
+  // past k are left alone. ts_split > 0 declares a stacked [R; B] tile: the
+  // first ts_split rows upper triangular. impl: "hand" (the panel kernels;
+  // wgs, poolA, apply and lookahead override qr_panel_wgs, qr_panel_poolA,
+  // qr_apply and qr_lookahead when not 0 / "" / -1), "rocsolver" or "cpu".
+  m.def("qr_factor_hip", [](py::array_t<double> A, int m, int k, int lda,
+                            int ts_split, std::string impl, int wgs,
+                            int poolA, std::string apply, int lookahead) {
+    static const std::map<std::string, int> impls = {
+        {"hand", 0}, {"rocsolver", 1}, {"cpu", 2}};
+    if (lda == 0) lda = m;
+    if (A.ndim() != 1 || k <= 0 || m < k || lda < m ||
+        A.size() < (py::ssize_t)lda * k)
+      throw std::invalid_argument(
+          "qr_factor_hip: 1-D buffer of at least lda*k, lda >= m >= k > 0");
+    if (ts_split != 0 && (ts_split < k || ts_split > m))
+      throw std::invalid_argument("qr_factor_hip: ts_split is 0 or in [k, m]");
+    auto it = impls.find(impl);
+    if (it == impls.end())
+      throw std::invalid_argument("qr_factor_hip: impl hand|rocsolver|cpu");
+    if (wgs != 0 && (wgs < 2 || wgs > 48))
+      throw std::invalid_argument("qr_factor_hip: wgs is 0 or in [2, 48]");
+    if (poolA < 0 || lookahead < -1 || lookahead > 1 ||
+        (!apply.empty() && apply != "kernel" && apply != "valu" &&
+         apply != "gemm"))
+      throw std::invalid_argument(
+          "qr_factor_hip: poolA >= 0, apply kernel|valu|gemm, lookahead "
+          "-1|0|1");
+    double* a = A.mutable_data();
+    size_t a_elems = (size_t)A.size();
+    py::array_t<double, py::array::f_style> T({k, k});
+    double* t = T.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      pa::test_qr_factor_hip(a, a_elems, m, k, lda, ts_split, it->second, wgs,
+                             poolA, apply, lookahead, t);
+    }
+    return T;
+  }, py::arg("A"), py::arg("m"), py::arg("k"), py::arg("lda") = 0,
+     py::arg("ts_split") = 0, py::arg("impl") = "hand", py::arg("wgs") = 0,
+     py::arg("poolA") = 0, py::arg("apply") = "", py::arg("lookahead") = -1);
   // ms per launch of the triangular X = B W^T kernel
   m.def("bench_dtrmm", [](int m, int n, int iters) {
     return pa::bench_dtrmm_hip(m, n, iters) / iters * 1e3;
