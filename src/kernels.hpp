@@ -26,6 +26,12 @@ struct TileArgs {
   uint32_t seed = 0;
 };
 
+// A task class with a CPU and a GPU incarnation, registered with the
+// profiler under `id` (kernels_blas.cpp). Every kernels_*.cpp builds its
+// classes through this.
+TaskClass make_tc(const char* name, TaskKind kind, void (*cpu)(Task&),
+                  void (*gpu)(Task&, GpuTaskCtx&), int id);
+
 // Registered once; ids stable.
 TaskClass& tc_spd_fill();
 TaskClass& tc_potrf();
@@ -89,6 +95,11 @@ void insert_reduce_sum_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& R);
 void insert_stencil_1d(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_panel_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_potrf_panel(Dtd& tp, TiledMatrix& A);
+
+// Most workgroups one panel-kernel launch may have. The kernel's workgroups
+// spin on each other's counters, so all of them must be resident at once,
+// and each takes a whole CU (about 150 KiB of LDS).
+constexpr int QR_PANEL_MAX_WGS = 48;
 
 // Test entry point of the QR panel factorization (kernels_qr.cpp): host
 // buffers in, factored A and the k x k T out. impl: 0 hand kernels, 1

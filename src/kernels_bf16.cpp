@@ -17,6 +17,7 @@
 
 #include "device_gpu.hpp"
 #include "kernels.hpp"
+#include "kernels_bench.hpp"
 #include "profiling.hpp"
 
 namespace pa {
@@ -608,24 +609,14 @@ static void gpu_gemm_bf16(Task& t, GpuTaskCtx& g) {
                    (float*)t.dev_ptr[2], ldc, g.stream, (int)a.j0);
 }
 
-static TaskClass make_bf_tc(const char* name, void (*cpu)(Task&),
-                            void (*gpu)(Task&, GpuTaskCtx&), int id) {
-  Profiler::inst().register_class(id, name);
-  TaskClass tc;
-  tc.name = name;
-  tc.kind = TaskKind::GPU;
-  tc.cpu_hook = cpu;
-  tc.gpu_hook = gpu;
-  tc.id = id;
-  return tc;
-}
-
 TaskClass& tc_fill_bf16() {
-  static TaskClass tc = make_bf_tc("fill_bf16", cpu_fill_bf16, gpu_fill_bf16, 20);
+  static TaskClass tc = make_tc("fill_bf16", TaskKind::GPU, cpu_fill_bf16,
+                                gpu_fill_bf16, 20);
   return tc;
 }
 TaskClass& tc_gemm_bf16() {
-  static TaskClass tc = make_bf_tc("gemm_bf16", cpu_gemm_bf16, gpu_gemm_bf16, 21);
+  static TaskClass tc = make_tc("gemm_bf16", TaskKind::GPU, cpu_gemm_bf16,
+                                gpu_gemm_bf16, 21);
   return tc;
 }
 
@@ -670,46 +661,27 @@ void insert_gemm_bf16(Dtd& tp, TiledMatrix& At, TiledMatrix& B,
 
 // kernel-level microbench (TFLOP/s)
 double bench_gemm_bf16(int m, int n, int k, int iters) {
-  bf16 *dA, *dB;
-  float* dC;
-  PA_HIP_CHECK(hipMalloc(&dA, (size_t)m * k * 2));
-  PA_HIP_CHECK(hipMalloc(&dB, (size_t)n * k * 2));
-  PA_HIP_CHECK(hipMalloc(&dC, (size_t)m * n * 4));
-  hipLaunchKernelGGL(k_fill_bf16, dim3(2048), dim3(256), 0, 0, dA,
+  DevArray<bf16> dA((size_t)m * k), dB((size_t)n * k);
+  DevArray<float> dC((size_t)m * n);
+  hipLaunchKernelGGL(k_fill_bf16, dim3(2048), dim3(256), 0, 0, dA.p,
                      (size_t)m * k, 1u);
-  hipLaunchKernelGGL(k_fill_bf16, dim3(2048), dim3(256), 0, 0, dB,
+  hipLaunchKernelGGL(k_fill_bf16, dim3(2048), dim3(256), 0, 0, dB.p,
                      (size_t)n * k, 2u);
-  PA_HIP_CHECK(hipMemset(dC, 0, (size_t)m * n * 4));
-  launch_gemm_bf16(m, n, k, dA, k, dB, k, dC, m, 0, 1);
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  double t0 = now_s();
-  for (int i = 0; i < iters; i++)
-    launch_gemm_bf16(m, n, k, dA, k, dB, k, dC, m, 0, 1);
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  double dt = now_s() - t0;
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dB));
-  PA_HIP_CHECK(hipFree(dC));
+  PA_HIP_CHECK(hipMemset(dC.p, 0, dC.bytes));
+  double dt = time_launches(iters, [&] {
+    launch_gemm_bf16(m, n, k, dA.p, k, dB.p, k, dC.p, m, 0, 1);
+  });
   return 2.0 * m * n * k * iters / dt / 1e12;
 }
 
 // host-I/O numerics harness
 void test_gemm_bf16_hip(int m, int n, int k, const uint16_t* A,
                         const uint16_t* B, float* C) {
-  bf16 *dA, *dB;
-  float* dC;
-  PA_HIP_CHECK(hipMalloc(&dA, (size_t)m * k * 2));
-  PA_HIP_CHECK(hipMalloc(&dB, (size_t)n * k * 2));
-  PA_HIP_CHECK(hipMalloc(&dC, (size_t)m * n * 4));
-  PA_HIP_CHECK(hipMemcpy(dA, A, (size_t)m * k * 2, hipMemcpyHostToDevice));
-  PA_HIP_CHECK(hipMemcpy(dB, B, (size_t)n * k * 2, hipMemcpyHostToDevice));
-  PA_HIP_CHECK(hipMemcpy(dC, C, (size_t)m * n * 4, hipMemcpyHostToDevice));
-  launch_gemm_bf16(m, n, k, dA, k, dB, k, dC, m, 0, 1);
-  PA_HIP_CHECK(hipGetLastError());
-  PA_HIP_CHECK(hipMemcpy(C, dC, (size_t)m * n * 4, hipMemcpyDeviceToHost));
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dB));
-  PA_HIP_CHECK(hipFree(dC));
+  DevArray<bf16> dA((size_t)m * k, (const bf16*)A),
+      dB((size_t)n * k, (const bf16*)B);
+  DevArray<float> dC((size_t)m * n, C);
+  launch_gemm_bf16(m, n, k, dA.p, k, dB.p, k, dC.p, m, 0, 1);
+  dC.download(C);
 }
 
 }  // namespace pa

@@ -16,6 +16,7 @@
 
 #include "device_gpu.hpp"
 #include "gpu_blas.hpp"
+#include "kernels_bench.hpp"
 #include "kernels_hip.hpp"
 #include "profiling.hpp"
 
@@ -328,40 +329,27 @@ static void gpu_gemm(Task& t, GpuTaskCtx& g) {
 
 // Timed rocBLAS dgemm NT loop for kernel-level A/B against the hand kernel.
 double bench_dgemm_rocblas(int m, int n, int k, int iters) {
-  double *dA, *dB, *dC;
-  PA_HIP_CHECK(hipMalloc(&dA, (size_t)m * k * 8));
-  PA_HIP_CHECK(hipMalloc(&dB, (size_t)n * k * 8));
-  PA_HIP_CHECK(hipMalloc(&dC, (size_t)m * n * 8));
-  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dA, m, k, m, 0,
-                     0, 0, 11u);
-  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dB, n, k, n, 7,
-                     3, 0, 12u);
-  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dC, m, n, m, 1,
-                     9, 0, 13u);
+  DevArray dA((size_t)m * k), dB((size_t)n * k), dC((size_t)m * n);
+  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dA.p, m, k, m,
+                     0, 0, 0, 11u);
+  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dB.p, n, k, n,
+                     7, 3, 0, 12u);
+  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dC.p, m, n, m,
+                     1, 9, 0, 13u);
   rocblas_handle h;
   PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
   const double mone = -1.0, one = 1.0;
-  auto run = [&] {
+  double dt = time_launches(iters, [&] {
     rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_transpose, m,
-                  n, k, &mone, dA, m, dB, n, &one, dC, m);
-  };
-  run();
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  double t0 = now_s();
-  for (int i = 0; i < iters; i++) run();
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  double dt = now_s() - t0;
+                  n, k, &mone, dA.p, m, dB.p, n, &one, dC.p, m);
+  });
   rocblas_destroy_handle(h);
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dB));
-  PA_HIP_CHECK(hipFree(dC));
   return dt;
 }
 
 // ------------------------------------------------------------------ classes
-static TaskClass make_tc(const char* name, TaskKind kind,
-                         void (*cpu)(Task&), void (*gpu)(Task&, GpuTaskCtx&),
-                         int id) {
+TaskClass make_tc(const char* name, TaskKind kind, void (*cpu)(Task&),
+                  void (*gpu)(Task&, GpuTaskCtx&), int id) {
   Profiler::inst().register_class(id, name);
   TaskClass tc;
   tc.name = name;
@@ -1659,13 +1647,10 @@ double bench_tn_rocblas(int kind, int m, int n, int k, int iters) {
   if (kind == 1 || kind == 3) m = n;
   if (kind >= 2) k = m;
   const size_t welems = (size_t)m * n;
-  double *dA, *dB, *dOrig, *dWork;
-  PA_HIP_CHECK(hipMalloc(&dA, (size_t)k * m * 8));
-  PA_HIP_CHECK(hipMalloc(&dB, (size_t)k * n * 8));
+  DevArray A((size_t)k * m), B((size_t)k * n), Orig(welems), Work(welems);
+  double *dA = A.p, *dB = B.p, *dOrig = Orig.p, *dWork = Work.p;
   hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dB, k, n, k, 5,
                      1, 0, 13u);
-  PA_HIP_CHECK(hipMalloc(&dOrig, welems * 8));
-  PA_HIP_CHECK(hipMalloc(&dWork, welems * 8));
   hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dA, k, m, k, 0,
                      0, 0, 11u);
   hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dOrig, m, n, m,
@@ -1711,10 +1696,6 @@ double bench_tn_rocblas(int kind, int m, int n, int k, int iters) {
   PA_HIP_CHECK(hipEventDestroy(e0));
   PA_HIP_CHECK(hipEventDestroy(e1));
   rocblas_destroy_handle(h);
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dB));
-  PA_HIP_CHECK(hipFree(dOrig));
-  PA_HIP_CHECK(hipFree(dWork));
   return total;
 }
 

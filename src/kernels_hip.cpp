@@ -40,6 +40,7 @@
 #include "kernels_hip.hpp"
 
 #include "kernels.hpp"
+#include "kernels_bench.hpp"
 
 namespace pa {
 
@@ -538,25 +539,6 @@ void launch_potf2(double* A, int n, int ld, hipStream_t stream) {
 // ------------------------------------------------ test and bench entries
 namespace {
 
-// A device array for the host-memory entry points: allocated, and uploaded
-// when a host image is given, on construction; freed on scope exit.
-struct DevArray {
-  double* p = nullptr;
-  size_t bytes;
-  explicit DevArray(size_t nelem, const double* host = nullptr)
-      : bytes(nelem * 8) {
-    PA_HIP_CHECK(hipMalloc(&p, bytes));
-    if (host) PA_HIP_CHECK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-  }
-  DevArray(const DevArray&) = delete;
-  ~DevArray() { PA_HIP_CHECK(hipFree(p)); }
-  // what the launches so far left in it (the copy waits for the null stream)
-  void download(double* host) {
-    PA_HIP_CHECK(hipGetLastError());
-    PA_HIP_CHECK(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost));
-  }
-};
-
 __global__ void k_bench_fill(double* p, size_t n, uint32_t seed) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -569,20 +551,9 @@ __global__ void k_bench_fill(double* p, size_t n, uint32_t seed) {
 }
 
 // random-ish fill (never bench on zero-filled operands — DVFS inflates)
-void bench_fill(DevArray& a, uint32_t seed) {
+void bench_fill(DevArray<double>& a, uint32_t seed) {
   hipLaunchKernelGGL(k_bench_fill, dim3(2048), dim3(256), 0, 0, a.p,
                      a.bytes / 8, seed);
-}
-
-// One warm-up launch, then the seconds that iters launches take.
-template <typename F>
-double time_launches(int iters, F run) {
-  run();
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  double t0 = now_s();
-  for (int i = 0; i < iters; i++) run();
-  PA_HIP_CHECK(hipDeviceSynchronize());
-  return now_s() - t0;
 }
 
 }  // namespace

@@ -267,14 +267,8 @@ void gpu_trsm_l_inv(Task& t, GpuTaskCtx& g) {
 TaskClass make_lu_tc(const char* name, void (*cpu)(Task&),
                      void (*gpu)(Task&, GpuTaskCtx&), int id,
                      bool blocking = false) {
-  Profiler::inst().register_class(id, name);
-  TaskClass tc;
-  tc.name = name;
-  tc.kind = TaskKind::GPU;
-  tc.cpu_hook = cpu;
-  tc.gpu_hook = gpu;
+  TaskClass tc = make_tc(name, TaskKind::GPU, cpu, gpu, id);
   tc.gpu_blocking = blocking;
-  tc.id = id;
   return tc;
 }
 

@@ -181,31 +181,21 @@ static void cpu_panel_update(Task& t) {
   t.flows[1].data->written_on(false);
 }
 
-static TaskClass make_pan_tc(const char* name, void (*cpu)(Task&),
-                             void (*gpu)(Task&, GpuTaskCtx&), int id) {
-  Profiler::inst().register_class(id, name);
-  TaskClass tc;
-  tc.name = name;
-  tc.kind = TaskKind::GPU;
-  tc.cpu_hook = cpu;
-  tc.gpu_hook = gpu;
-  tc.id = id;
-  return tc;
-}
-
 TaskClass& tc_panel_fill() {
   static TaskClass tc =
-      make_pan_tc("panel_fill", cpu_panel_fill, gpu_panel_fill, 40);
+      make_tc("panel_fill", TaskKind::GPU, cpu_panel_fill, gpu_panel_fill, 40);
   return tc;
 }
 TaskClass& tc_panel_factor() {
   static TaskClass tc =
-      make_pan_tc("panel_factor", cpu_panel_factor, gpu_panel_factor, 41);
+      make_tc("panel_factor", TaskKind::GPU, cpu_panel_factor,
+              gpu_panel_factor, 41);
   return tc;
 }
 TaskClass& tc_panel_update() {
   static TaskClass tc =
-      make_pan_tc("panel_update", cpu_panel_update, gpu_panel_update, 42);
+      make_tc("panel_update", TaskKind::GPU, cpu_panel_update,
+              gpu_panel_update, 42);
   return tc;
 }
 

@@ -25,6 +25,7 @@
 #include "device_gpu.hpp"
 #include "gpu_blas.hpp"
 #include "kernels.hpp"
+#include "kernels_bench.hpp"
 #include "profiling.hpp"
 
 namespace pa {
@@ -214,6 +215,25 @@ __global__ void k_qr_fill(double* p, size_t n, uint32_t seed) {
   }
 }
 
+// Slots of qr_scratch: one growing device buffer per (stream, slot). Every
+// user of a slot enqueues on the stream that keys it, so two users of one
+// slot are ordered by the stream and the second finds the first one's work
+// done. That is all that makes the shared slots below safe.
+enum QrSlot {
+  QR_SLOT_TAU = 0,       // tau of the tile (hand and rocSOLVER routes)
+  QR_SLOT_V = 1,         // unit-lower V for G = V^T V; also TSMQR's stacked S
+  QR_SLOT_G128 = 2,      // G of one 128-column panel
+  QR_SLOT_T128 = 3,      // T of one 128-column panel
+  QR_SLOT_LARFB = 4,     // larfb_gemm's V, W, W2 (4, 5, 6): panels and UNMQR
+  QR_SLOT_G = 7,         // G over all k columns
+  QR_SLOT_X = 8,         // blocked T combine
+  QR_SLOT_T16S = 9,      // the panel kernel's 16x16 T blocks
+  QR_SLOT_CNT = 10,      // the panel kernel's publish/ack counters
+  // TSMQR's larfb_gemm (8, 9, 10) shares X, T16S and CNT on purpose: a
+  // factorization and a TSMQR never overlap on one stream.
+  QR_SLOT_LARFB_TS = 8,
+};
+
 double* qr_scratch(GpuTaskCtx& g, int slot, size_t bytes) {
   static thread_local std::map<std::pair<void*, int>,
                                std::pair<void*, size_t>> bufs;
@@ -285,10 +305,45 @@ inline dim3 grid1d(int total) {
 }  // namespace
 
 __global__ void k_unitlow(double* V, const double* A, int m, int k, int lda,
-                          int ldv);
+                          int ldv) {
+  // V = unit-lower copy of A's reflector block (zeros above, 1 on diag)
+  int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  int total = m * k;
+  for (; idx < total; idx += gridDim.x * blockDim.x) {
+    int c = idx / m, r = idx - c * m;
+    double v = r < c ? 0.0 : (r == c ? 1.0 : A[(size_t)c * lda + r]);
+    V[(size_t)c * ldv + r] = v;
+  }
+}
+
+// C = (I - V T V^T)^T C via three full-rate dgemms (rocSOLVER's dlarfb
+// decomposes into micro-kernels at these sizes: profiles/RESULTS.md).
+// V: m x k reflectors (unit-lower inside A-storage), T: k x k upper
+// (zeros elsewhere), C: m x n. Scratch: V expanded, W and W2 (k x n) in the
+// three slots from `slot` on.
 static void larfb_gemm(GpuTaskCtx& g, int m, int n, int k, const double* A,
                        int lda, const double* T, int ldt, double* C, int ldc,
-                       int scratch_slot);
+                       QrSlot slot) {
+  rocblas_handle h = blas_handle(g);
+  double* V = qr_scratch(g, slot, (size_t)m * k * 8);
+  double* W = qr_scratch(g, slot + 1, (size_t)k * n * 8);
+  hipLaunchKernelGGL(k_unitlow, grid1d(m * k), dim3(256), 0, g.stream, V, A,
+                     m, k, lda, m);
+  const double one = 1.0, zero = 0.0, mone = -1.0;
+  // W = V^T C
+  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                         rocblas_operation_none, k, n, m, &one, V, m, C, ldc,
+                         &zero, W, k) == rocblas_status_success);
+  // W = T^T W  (T upper-triangular, stored dense with zero lower)
+  double* W2 = qr_scratch(g, slot + 2, (size_t)k * n * 8);
+  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                         rocblas_operation_none, k, n, k, &one, T, ldt, W, k,
+                         &zero, W2, k) == rocblas_status_success);
+  // C -= V W2
+  PA_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
+                         m, n, k, &mone, V, m, W2, k, &one, C,
+                         ldc) == rocblas_status_success);
+}
 
 // ---------------------------------------------------------- hand panel QR
 // rocSOLVER's dgeqrf at tile sizes runs an unblocked host-synced column
@@ -362,18 +417,31 @@ __global__ void __launch_bounds__(1024) k_geqr2(double* A, int m, int ncols,
 
 // ---------------------------------------------------- multi-WG panel QR
 // One LAUNCH factors a whole 128-column panel (vs k_geqr2's one-WG column
-// loop at 0.7 TF, profiles/RESULTS.md): WG 0 factors 16-column sub-panels
-// held in LDS (fast column loop: norm reduce + rank-1 updates never leave
-// the CU), builds the 16x16 T block in LDS, then ALL workgroups apply the
-// block reflector to the remaining panel columns between agent-scope grid
-// barriers (MI355X_MICROARCH.md "Workgroup dispatch" release/acquire
-// forms). A two-segment row map skips the structurally-zero block of
-// stacked [R (upper-tri); B] TSQRT tiles, capping active rows at
-// top_block + B regardless of the panel offset.
+// loop at 0.7 TF, profiles/RESULTS.md) as a producer/consumer pipeline
+// with no grid-wide barrier:
+//  - WG 0 factors 16-column sub-panels held in LDS (norm reduce + rank-1
+//    updates never leave the CU; one barrier per column, piggybacked norms,
+//    deferred scaling), builds the 16x16 T block from a parallel
+//    G = V^T V, then PUBLISHES the sub-panel: cnt[0] = si + 1.
+//  - helper pool A (WGs 1..nA) applies each published block reflector to
+//    the remaining FACTOR columns and ACKS: cnt[1] += 1. WG 0 only stages
+//    sub-panel s+1 after ack(s), so the factor chain never waits on the
+//    trailing matrix.
+//  - pool B (the rest) streams the same applies over the trailing columns
+//    asynchronously, in publication order (each column has a fixed owner,
+//    so per-column apply order is the program order).
+// Memory protocol per MI355X_MICROARCH.md "Workgroup dispatch": plain
+// stores -> release fence + vmcnt(0) asm -> relaxed counter; consumers
+// poll relaxed, acquire-fence once, then plain loads. Waiters spin, so all
+// nwg workgroups must be resident at once (QR_PANEL_MAX_WGS).
 //
-// Row map: local row r < len0 -> global base0 + r ; else base1 + (r-len0).
+// A two-segment row map skips the structurally-zero block of stacked
+// [R (upper-tri); B] TSQRT tiles, capping active rows at top_block + B
+// regardless of the panel offset.
 // LDS budget: rows * W * 8 <= 147456 (W=16 up to 1152 rows, W=8 to 2304).
 namespace {
+
+#define QR_DEV __device__ __forceinline__
 
 constexpr int QR_LDS_DOUBLES = 18432;  // 144 KiB panel + ~8 KiB reduction
 constexpr int QR_MAX_ROWS_W16 = 1152;
@@ -382,55 +450,402 @@ constexpr int QR_MAX_ROWS_W8 = 2304;
 // sub-panels at W=16 and 16 at W=8.
 constexpr int QR_MAX_SUBPANELS = 16;
 
-__device__ inline void qr_grid_barrier(int* cnt, int nwg, int bar_no) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (__hip_atomic_load(cnt, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT) < bar_no * nwg)
-      __builtin_amdgcn_s_sleep(8);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+// Row map: local row r < len0 -> global base0 + r ; else base1 + (r-len0).
+struct QrRowMap {
+  int base0, len0, base1, len1;
+  __host__ __device__ int rows() const { return len0 + len1; }
+  QR_DEV int global_row(int r) const {
+    return r < len0 ? base0 + r : base1 + (r - len0);
   }
-  __syncthreads();
+  // Global column gcol as two pointers, BOTH indexed by local row: seg0[r]
+  // for r < len0, seg1[r] for r >= len0.
+  QR_DEV double* seg0(double* A, int ld, int gcol) const {
+    return A + (size_t)gcol * ld + base0;
+  }
+  QR_DEV double* seg1(double* A, int ld, int gcol) const {
+    return A + (size_t)gcol * ld + base1 - len0;
+  }
+};
+
+struct QrPanelArgs {
+  double* A;
+  int ld;
+  int pcol0;     // panel base column (global)
+  QrRowMap rm;   // reflector row segments
+  int pc;        // total columns from pcol0 (factor + apply targets)
+  int fcols;     // columns to FACTOR (<=128)
+  int W;         // sub-panel width (8|16)
+  double* tau;   // of the panel's columns
+  double* T16s;  // 16x16 per sub-panel
+  int* cnt;      // [0] sub-panels published, [1] pool A acks
+  int nwg, nA, amode, look;
+  unsigned long long* dbg;  // phase timers (bench_qr_factor), or null
+};
+
+// Householder parameters of a column with diagonal entry alpha and squared
+// norm nrm2 below it: the unscaled reflector is (vd, x), beta replaces
+// alpha, and tfac = tau / vd^2 applies it before the deferred scaling.
+struct QrHouse {
+  double vd, beta, tfac, tau;
+};
+QR_DEV QrHouse qr_house(double alpha, double nrm2) {
+  QrHouse h{1.0, alpha, 0.0, 0.0};
+  if (nrm2 != 0.0) {
+    h.beta = -copysign(sqrt(alpha * alpha + nrm2), alpha);
+    h.vd = alpha - h.beta;
+    h.tau = (h.beta - alpha) / h.beta;
+    h.tfac = h.tau / (h.vd * h.vd);
+  }
+  return h;
 }
 
-// A panel column's reflector value at local row r (unit-lower, in-place).
-__device__ inline double qr_vval(const double* A, int ld, int base0,
-                                 int len0, int base1, int r, int cloc,
-                                 int gcol) {
-  if (r < cloc) return 0.0;
-  if (r == cloc) return 1.0;
-  int gr = r < len0 ? base0 + r : base1 + (r - len0);
-  return A[(size_t)gcol * ld + gr];
+// Release side, one lane: what this workgroup stored before its last
+// barrier is visible to whoever then reads the counter.
+QR_DEV void qr_release() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+QR_DEV void qr_publish(int* cnt, int value) {
+  qr_release();
+  __hip_atomic_store(cnt, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+QR_DEV void qr_signal_add(int* cnt) {
+  qr_release();
+  __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Acquire side, one lane; the caller's barrier then lets the others read.
+QR_DEV void qr_wait_ge(int* cnt, int value) {
+  while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+         value)
+    __builtin_amdgcn_s_sleep(2);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+// Phase timer of bench_qr_factor's timed mode: lap(slot) adds the ticks
+// since the previous lap to dbg[slot]. A no-op when dbg is null.
+struct QrTimer {
+  unsigned long long* dbg;
+  unsigned long long t0;
+  QR_DEV explicit QrTimer(unsigned long long* d)
+      : dbg(d), t0(d ? __builtin_amdgcn_s_memrealtime() : 0) {}
+  QR_DEV void lap(int slot) {
+    if (!dbg) return;
+    unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
+    dbg[slot] += t1 - t0;
+    t0 = t1;
+  }
+};
 
 typedef double f64x4q __attribute__((ext_vector_type(4)));
 
-// MFMA block-reflector apply used by the panel kernel's helper pool:
-// processes 16 columns at once through v_mfma_f64_16x16x4f64, staging
-// 256-row chunks of the (unit-lower) V image and of C in LDS carved from
-// `sp` — W = V^T C and C -= V Y become matrix-core work instead of
-// latency-bound 16-lane dot units (profiles/qr_round2.md headroom note).
-// Layout notes: operands stored [k][m] in LDS ([row*16 + q] for V), MFMA
-// lane map a = A[m=r16][k=ksub], D(row=ksub+4e, col=r16) — the repo's
-// fp64 GEMM conventions (kernels_hip.cpp).
-__device__ void qr_apply_mfma16(
-    double* A, int ld, int pcol0, int base0, int len0, int base1, int rows,
-    int c0, int w, const double* T16, const int* cg, int nc, double* sp,
-    double* wy /*unused*/, int tid, int wave, int lane) {
-  double* Vc = sp;               // [256][16]
-  double* Cc = sp + 256 * 16;    // [256][16]
-  double* Wr = sp + 2 * 256 * 16;  // [16 waves][16][16] partial W
-  double* Ys = sp + 2 * 256 * 16 + 16 * 256;  // [16][16] col-major [c][q]
-  const int r16 = lane & 15, ksub = lane >> 4;
+// One thread's view of the panel kernel: the launch arguments, the shared
+// arrays (declared in k_qr_panel_mw), its ids, and the current sub-panel.
+struct QrPanel : QrPanelArgs {
+  double* sp;   // sub-panel / V image
+  double* red;  // norm partials (staging)
+  double* bcs;  // per-col {vd, beta, tfac}
+  double* tl;   // per-col tau (LDS copy)
+  double* wy;   // dots + y for 4 columns
+  double* gt;   // G (16x16) + local T (16x16)
+  int tid, wave, lane;
+  int len0, rows;
+  int c0, w;    // first column and width of sub-panel si
+  double* T16;  // its T block
 
-  // ---------------- step A: W = V^T C ----------------
-  f64x4q accW = {0, 0, 0, 0};
-  for (int ck = 0; ck < rows; ck += 256) {
-    const int clen = min(256, rows - ck);
-    // stage V chunk (transposed [r][q], unit-lower semantics, zero pad)
+  QR_DEV int subpanels() const { return (fcols + W - 1) / W; }
+  QR_DEV void select(int si) {
+    c0 = si * W;
+    w = min(W, fcols - c0);
+    T16 = T16s + (size_t)si * 256;
+  }
+  QR_DEV void set_house(int j, const QrHouse& h) {
+    bcs[3 * j] = h.vd;
+    bcs[3 * j + 1] = h.beta;
+    bcs[3 * j + 2] = h.tfac;
+    tl[j] = h.tau;
+    tau[c0 + j] = h.tau;
+  }
+
+  // ------------------------------------------------------------- WG 0
+  // Step 1: stage the sub-panel's columns into LDS, reducing the first
+  // column's norm on the way; thread 0 sets up that column's reflector.
+  QR_DEV void stage() {
+    double acc0 = 0;
+    for (int q = 0; q < w; q++) {
+      const double* A0 = rm.seg0(A, ld, pcol0 + c0 + q);
+      const double* A1 = rm.seg1(A, ld, pcol0 + c0 + q);
+      double* spq = sp + (size_t)q * rows;
+      for (int r = tid; r < len0; r += 1024) {
+        double v = A0[r];
+        spq[r] = v;
+        if (q == 0 && r > c0) acc0 += v * v;
+      }
+      for (int r = len0 + tid; r < rows; r += 1024) {
+        double v = A1[r];
+        spq[r] = v;
+        if (q == 0) acc0 += v * v;
+      }
+    }
+    for (int sh = 32; sh > 0; sh >>= 1) acc0 += __shfl_down(acc0, sh);
+    if (lane == 0) red[wave] = acc0;
+    __syncthreads();
+    if (tid == 0) {
+      double nrm2 = 0;
+      for (int v = 0; v < 16; v++) nrm2 += red[v];
+      set_house(0, qr_house(sp[c0], nrm2));
+    }
+    __syncthreads();
+  }
+
+  // Step 2: the column loop, one barrier per column. Wave q > j applies
+  // reflector j to column q; wave j + 1 reduces the next column's norm
+  // while it updates it, and sets up reflector j + 1.
+  QR_DEV void factor_columns() {
+    for (int j = 0; j < w; j++) {
+      const int d = c0 + j;
+      const double vd = bcs[3 * j], tfac = bcs[3 * j + 2];
+      if (wave > j && wave < w) {
+        const double* col = sp + (size_t)j * rows;
+        double* cc = sp + (size_t)wave * rows;
+        double dot = (lane == 0) ? vd * cc[d] : 0.0;
+        double dot1 = 0.0;
+        for (int i = d + 1 + lane; i < rows; i += 128) dot += col[i] * cc[i];
+        for (int i = d + 65 + lane; i < rows; i += 128)
+          dot1 += col[i] * cc[i];
+        dot += dot1;
+        for (int sh = 32; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh);
+        dot = __shfl(dot, 0);
+        const double wj = tfac * dot;
+        if (lane == 0) cc[d] -= wj * vd;
+        double nacc = 0;
+        const bool mine = (wave == j + 1);
+        for (int i = d + 1 + lane; i < rows; i += 64) {
+          double nv = cc[i] - wj * col[i];
+          cc[i] = nv;
+          if (mine && i > d + 1) nacc += nv * nv;
+        }
+        if (mine) {
+          for (int sh = 32; sh > 0; sh >>= 1) nacc += __shfl_down(nacc, sh);
+          if (lane == 0) set_house(j + 1, qr_house(cc[d + 1], nacc));
+        }
+      }
+      __syncthreads();
+    }
+  }
+
+  // Step 3: the deferred scaling (v = x / vd, beta on the diagonal), then
+  // the factored columns go back to global memory.
+  QR_DEV void scale_writeback() {
+    if (wave < w) {
+      const int d = c0 + wave;
+      double* col = sp + (size_t)wave * rows;
+      const double inv = 1.0 / bcs[3 * wave];
+      for (int i = d + 1 + lane; i < rows; i += 64) col[i] *= inv;
+      if (lane == 0) col[d] = bcs[3 * wave + 1];
+    }
+    __syncthreads();
+    for (int q = 0; q < w; q++) {
+      double* A0 = rm.seg0(A, ld, pcol0 + c0 + q);
+      double* A1 = rm.seg1(A, ld, pcol0 + c0 + q);
+      const double* spq = sp + (size_t)q * rows;
+      for (int r = tid; r < len0; r += 1024) A0[r] = spq[r];
+      for (int r = len0 + tid; r < rows; r += 1024) A1[r] = spq[r];
+    }
+    __syncthreads();
+  }
+
+  // Step 4: G = V^T V by 64 units of 16 lanes over the (sc < q) pairs, then
+  // wave 0 runs the T recurrence in LDS and writes the 16x16 block out.
+  QR_DEV void build_t16() {
+    const int unit = wave * 4 + (lane >> 4), l16 = lane & 15;
+    const int npairs = w * (w - 1) / 2;
+    for (int idx = unit; idx < npairs; idx += 64) {
+      // decode idx -> (sq pair): q = row in triangle
+      int q = 1;
+      int rem = idx;
+      while (rem >= q) {
+        rem -= q;
+        q++;
+      }
+      int sc = rem;  // 0 <= sc < q
+      const int dq = c0 + q;
+      const double* cs = sp + (size_t)sc * rows;
+      const double* cq = sp + (size_t)q * rows;
+      // i >= dq > ds always: v_s = cs[i]; v_q = 1 at dq, cq[i] below
+      double dot = (l16 == 0) ? cs[dq] : 0.0;
+      double d1 = 0.0;
+      for (int i = dq + 1 + l16; i < rows; i += 32) dot += cs[i] * cq[i];
+      for (int i = dq + 17 + l16; i < rows; i += 32) d1 += cs[i] * cq[i];
+      dot += d1;
+      for (int sh = 8; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh, 16);
+      if (l16 == 0) gt[sc * 16 + q] = dot;  // G(sc, q)
+    }
+    __syncthreads();
+    if (wave == 0) {
+      double* Tl = gt + 256;
+      const double* G = gt;
+      for (int j = 0; j < w; j++) {
+        double tj = tl[j];
+        double sacc = 0;
+        if (lane < j) {
+          for (int q = lane; q < j; q++)
+            sacc += Tl[q * 16 + lane] * G[q * 16 + j];
+          sacc *= -tj;
+        }
+        if (lane < j) Tl[j * 16 + lane] = sacc;
+        if (lane == j) Tl[j * 16 + j] = tj;
+      }
+      if (lane < 16)
+        for (int j = 0; j < 16; j++)
+          T16[j * 16 + lane] =
+              (j < w && lane <= j) ? Tl[j * 16 + lane] : 0.0;
+    }
+    __syncthreads();
+  }
+
+  // ------------------------------- VALU apply of the block reflector
+  // (I - V T V^T)^T on up to four columns at a time, V read from sp:
+  //  1. dots: the 16-lane unit (wave q, group ci) reduces w_q = v_q . C_ci
+  //     into wy[ci * 16 + q];
+  //  2. y = T^T w into wy[64 + ci * 16 + q];
+  //  3. C_ci -= V y, 256 threads per column.
+  // Phase 1 sums in a different order on WG 0 and on the helpers, so it
+  // stays two functions; phases 2 and 3 are shared.
+
+  // Phase 1 on WG 0's raw sub-panel (R above the diagonal, no unit diagonal
+  // stored): start below the diagonal and add the diagonal term by hand.
+  // Two partial sums at stride 32.
+  QR_DEV void dots_raw(int gcol, int ci) {
+    const int l16 = lane & 15, cloc = c0 + wave;
+    const double* v = sp + (size_t)wave * rows;
+    const double* A0 = rm.seg0(A, ld, gcol);
+    const double* A1 = rm.seg1(A, ld, gcol);
+    double dot = (l16 == 0) ? A0[cloc] : 0.0;
+    double d1 = 0;
+    for (int r = cloc + 1 + l16; r < len0; r += 32) dot += v[r] * A0[r];
+    for (int r = cloc + 17 + l16; r < len0; r += 32) d1 += v[r] * A0[r];
+    for (int r = len0 + l16; r < rows; r += 32) dot += v[r] * A1[r];
+    for (int r = len0 + 16 + l16; r < rows; r += 32) d1 += v[r] * A1[r];
+    dot += d1;
+    for (int sh = 8; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh, 16);
+    if (l16 == 0) wy[ci * 16 + wave] = dot;
+  }
+
+  // Phase 1 on a helper's unit-lower V image: four partial sums at stride
+  // 64.
+  QR_DEV void dots_image(int gcol, int ci) {
+    const int l16 = lane & 15, cloc = c0 + wave;
+    const double* v = sp + (size_t)wave * rows;
+    const double* A0 = rm.seg0(A, ld, gcol);
+    const double* A1 = rm.seg1(A, ld, gcol);
+    double d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+    for (int r = cloc + l16; r < len0; r += 64) d0 += v[r] * A0[r];
+    for (int r = cloc + 16 + l16; r < len0; r += 64) d1 += v[r] * A0[r];
+    for (int r = cloc + 32 + l16; r < len0; r += 64) d2 += v[r] * A0[r];
+    for (int r = cloc + 48 + l16; r < len0; r += 64) d3 += v[r] * A0[r];
+    for (int r = len0 + l16; r < rows; r += 64) d0 += v[r] * A1[r];
+    for (int r = len0 + 16 + l16; r < rows; r += 64) d1 += v[r] * A1[r];
+    for (int r = len0 + 32 + l16; r < rows; r += 64) d2 += v[r] * A1[r];
+    for (int r = len0 + 48 + l16; r < rows; r += 64) d3 += v[r] * A1[r];
+    double dot = (d0 + d1) + (d2 + d3);
+    for (int sh = 8; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh, 16);
+    if (l16 == 0) wy[ci * 16 + wave] = dot;
+  }
+
+  // Phases 2 and 3 for nc columns, column i being panel column col(i).
+  // RAW_SP: sp is WG 0's raw sub-panel, so the unit-lower mask is applied
+  // on the fly in the top segment; a helper's image has it built in.
+  template <bool RAW_SP, typename ColOf>
+  QR_DEV void apply_finish(int nc, ColOf col) {
+    __syncthreads();
+    if (tid < 16 * nc) {
+      const int q = tid & 15, c = tid >> 4;
+      double sacc = 0;
+      for (int p2 = 0; p2 <= q; p2++)
+        sacc += T16[q * 16 + p2] * wy[c * 16 + p2];
+      wy[64 + c * 16 + q] = sacc;
+    }
+    __syncthreads();
+    const int c = tid >> 8, t2 = tid & 255;  // 4 cols x 256 threads
+    if (c < nc) {
+      double* A0 = rm.seg0(A, ld, pcol0 + col(c));
+      double* A1 = rm.seg1(A, ld, pcol0 + col(c));
+      const double* y = wy + 64 + c * 16;
+      for (int r = c0 + t2; r < len0; r += 256) {
+        double sacc = 0;
+        for (int q = 0; q < w; q++) {
+          double v = sp[(size_t)q * rows + r];
+          if (RAW_SP) v = r < c0 + q ? 0.0 : (r == c0 + q ? 1.0 : v);
+          sacc += v * y[q];
+        }
+        A0[r] -= sacc;
+      }
+      for (int r = len0 + t2; r < rows; r += 256) {
+        double sacc = 0;
+        for (int q = 0; q < w; q++) sacc += sp[(size_t)q * rows + r] * y[q];
+        A1[r] -= sacc;
+      }
+    }
+    __syncthreads();
+  }
+
+  // Step 6: apply this block to the NEXT sub-panel's columns, so that pool
+  // A's pass over them is off the factor chain.
+  QR_DEV void self_apply() {
+    const int cend = min(c0 + 2 * W, fcols), ci = lane >> 4;
+    for (int c = c0 + w; look && c < cend; c += 4) {
+      const int nc = min(4, cend - c);
+      if (ci < nc && wave < w) dots_raw(pcol0 + c + ci, ci);
+      apply_finish<true>(nc, [=](int i) { return c + i; });
+    }
+  }
+
+  QR_DEV void run_wg0() {
+    for (int si = 0; si < subpanels(); si++) {
+      select(si);
+      QrTimer tm(tid == 0 ? dbg : nullptr);
+      stage();
+      tm.lap(1);
+      factor_columns();
+      tm.lap(2);
+      scale_writeback();
+      tm.lap(3);
+      build_t16();
+      tm.lap(4);
+      // Step 5: publish sub-panel si, then wait for pool A to finish
+      // sub-panel si-1 everywhere: its range [c0-W+2W, fcols) includes OUR
+      // self-apply window, and the si-1 reflectors must land on those
+      // columns before si's do. The factor of si overlapped pool A's si-1
+      // pass, so this wait is the pipeline's only rendezvous. With
+      // qr_lookahead=0 the self-apply is off and the wait covers pool A
+      // through si instead.
+      if (tid == 0) {
+        qr_publish(&cnt[0], si + 1);
+        qr_wait_ge(&cnt[1], (si + (look ? 0 : 1)) * nA);
+      }
+      __syncthreads();
+      tm.lap(0);
+      self_apply();
+    }
+  }
+
+  // ------------------------------------------------ helper workgroups
+  // Cache the scaled V image (unit-lower) of the published sub-panel.
+  QR_DEV void build_v_image() {
+    for (int q = 0; q < w; q++) {
+      const int cloc = c0 + q;
+      const double* A0 = rm.seg0(A, ld, pcol0 + cloc);
+      const double* A1 = rm.seg1(A, ld, pcol0 + cloc);
+      double* spq = sp + (size_t)q * rows;
+      for (int r = tid; r < len0; r += 1024)
+        spq[r] = r < cloc ? 0.0 : (r == cloc ? 1.0 : A0[r]);
+      for (int r = len0 + tid; r < rows; r += 1024) spq[r] = A1[r];
+    }
+  }
+
+  // Rows [ck, ck + clen) of V into Vc, transposed [r][q] with unit-lower
+  // semantics, zero-padded to 256 x 16.
+  QR_DEV void stage_v_chunk(int ck, int clen, double* Vc) {
     for (int x = tid; x < 256 * 16; x += 1024) {
       const int q = x >> 8, rr = x & 255;
       const int r = ck + rr;
@@ -440,26 +855,43 @@ __device__ void qr_apply_mfma16(
         if (r == cloc) {
           v = 1.0;
         } else if (r > cloc) {
-          int gr = r < len0 ? base0 + r : base1 + (r - len0);
-          v = A[(size_t)(pcol0 + cloc) * ld + gr];
+          v = A[(size_t)(pcol0 + cloc) * ld + rm.global_row(r)];
         }
       }
       Vc[rr * 16 + q] = v;
     }
-    // stage C chunk ([r][c], zero pad)
-    for (int x = tid; x < 256 * 16; x += 1024) {
-      const int c = x >> 8, rr = x & 255;
-      const int r = ck + rr;
-      double v = 0;
-      if (rr < clen && c < nc) {
-        int gr = r < len0 ? base0 + r : base1 + (r - len0);
-        v = A[(size_t)(pcol0 + cg[c]) * ld + gr];
+  }
+
+  // MFMA block-reflector apply for up to 16 columns cg[0..nc) at once
+  // through v_mfma_f64_16x16x4f64, staging 256-row chunks of the V image
+  // and of C in LDS carved from sp: W = V^T C and C -= V Y become
+  // matrix-core work instead of latency-bound 16-lane dot units
+  // (profiles/qr_round2.md headroom note).
+  // Layout notes: operands stored [k][m] in LDS ([row*16 + q] for V), MFMA
+  // lane map a = A[m=r16][k=ksub], D(row=ksub+4e, col=r16): the repo's fp64
+  // GEMM conventions (kernels_hip.cpp).
+  __device__ void apply_mfma16(const int* cg, int nc) {
+    double* Vc = sp;               // [256][16]
+    double* Cc = sp + 256 * 16;    // [256][16]
+    double* Wr = sp + 2 * 256 * 16;  // [16 waves][16][16] partial W
+    double* Ys = sp + 2 * 256 * 16 + 16 * 256;  // [16][16] col-major [c][q]
+    const int r16 = lane & 15, ksub = lane >> 4;
+
+    // ---------------- step A: W = V^T C ----------------
+    f64x4q accW = {0, 0, 0, 0};
+    for (int ck = 0; ck < rows; ck += 256) {
+      const int clen = min(256, rows - ck);
+      stage_v_chunk(ck, clen, Vc);
+      // stage C chunk ([r][c], zero pad)
+      for (int x = tid; x < 256 * 16; x += 1024) {
+        const int c = x >> 8, rr = x & 255;
+        double v = 0;
+        if (rr < clen && c < nc)
+          v = A[(size_t)(pcol0 + cg[c]) * ld + rm.global_row(ck + rr)];
+        Cc[rr * 16 + c] = v;
       }
-      Cc[rr * 16 + c] = v;
-    }
-    __syncthreads();
-    // wave `wave` covers k-rows [wave*16, wave*16+16) of this chunk
-    {
+      __syncthreads();
+      // wave `wave` covers k-rows [wave*16, wave*16+16) of this chunk
       const int k0 = wave * 16;
 #pragma unroll
       for (int kk = 0; kk < 16; kk += 4) {
@@ -467,535 +899,154 @@ __device__ void qr_apply_mfma16(
         double b = Cc[(k0 + kk + ksub) * 16 + r16];
         accW = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, accW, 0, 0, 0);
       }
+      __syncthreads();
     }
-    __syncthreads();
-  }
-  // reduce the 16 per-wave W partials, then Y = T^T W
+    // reduce the 16 per-wave W partials, then Y = T^T W
 #pragma unroll
-  for (int e = 0; e < 4; e++)
-    Wr[wave * 256 + (ksub + 4 * e) * 16 + r16] = accW[e];
-  __syncthreads();
-  if (tid < 256) {
-    const int q = tid & 15, c = tid >> 4;
-    double wsum = 0;
-    for (int wv = 0; wv < 16; wv++) wsum += Wr[wv * 256 + q * 16 + c];
-    // stash W(q, c) back (reuse Wr row 0 region is unsafe; use Ys then
-    // overwrite with Y below via a second barrier)
-    Wr[q * 16 + c] = wsum;  // W in [q][c] at the front of Wr
-  }
-  __syncthreads();
-  if (tid < 256) {
-    const int q = tid & 15, c = tid >> 4;
-    double y = 0;
-    for (int p2 = 0; p2 <= q; p2++) y += T16[q * 16 + p2] * Wr[p2 * 16 + c];
-    Ys[(q)*16 + c] = y;  // Y stored [k=q][c]
-  }
-  __syncthreads();
-
-  // ---------------- step B: C -= V * Y ----------------
-  for (int ck = 0; ck < rows; ck += 256) {
-    const int clen = min(256, rows - ck);
-    for (int x = tid; x < 256 * 16; x += 1024) {
-      const int q = x >> 8, rr = x & 255;
-      const int r = ck + rr;
-      double v = 0;
-      if (rr < clen && q < w) {
-        const int cloc = c0 + q;
-        if (r == cloc) {
-          v = 1.0;
-        } else if (r > cloc) {
-          int gr = r < len0 ? base0 + r : base1 + (r - len0);
-          v = A[(size_t)(pcol0 + cloc) * ld + gr];
-        }
-      }
-      Vc[rr * 16 + q] = v;
+    for (int e = 0; e < 4; e++)
+      Wr[wave * 256 + (ksub + 4 * e) * 16 + r16] = accW[e];
+    __syncthreads();
+    if (tid < 256) {
+      const int q = tid & 15, c = tid >> 4;
+      double wsum = 0;
+      for (int wv = 0; wv < 16; wv++) wsum += Wr[wv * 256 + q * 16 + c];
+      // W(q, c) lands in [q][c] at the front of Wr: a word that only this
+      // thread reads in this step
+      Wr[q * 16 + c] = wsum;
     }
     __syncthreads();
-    // wave owns the 16-row m-tile [wave*16, wave*16+16) of the chunk
-    f64x4q accU = {0, 0, 0, 0};
-    {
+    if (tid < 256) {
+      const int q = tid & 15, c = tid >> 4;
+      double y = 0;
+      for (int p2 = 0; p2 <= q; p2++) y += T16[q * 16 + p2] * Wr[p2 * 16 + c];
+      Ys[(q)*16 + c] = y;  // Y stored [k=q][c]
+    }
+    __syncthreads();
+
+    // ---------------- step B: C -= V * Y ----------------
+    for (int ck = 0; ck < rows; ck += 256) {
+      const int clen = min(256, rows - ck);
+      stage_v_chunk(ck, clen, Vc);
+      __syncthreads();
+      // wave owns the 16-row m-tile [wave*16, wave*16+16) of the chunk
+      f64x4q accU = {0, 0, 0, 0};
 #pragma unroll
       for (int kk = 0; kk < 16; kk += 4) {
         double a = Vc[(wave * 16 + r16) * 16 + kk + ksub];
         double b = Ys[(kk + ksub) * 16 + r16];
         accU = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, accU, 0, 0, 0);
       }
-    }
-    // D(row=ksub+4e, col=r16) -> Cc[(wave*16+row)][col]
+      // D(row=ksub+4e, col=r16) -> Cc[(wave*16+row)][col]
 #pragma unroll
-    for (int e = 0; e < 4; e++)
-      Cc[(wave * 16 + ksub + 4 * e) * 16 + r16] = accU[e];
-    __syncthreads();
-    // coalesced global RMW per column
-    for (int x = tid; x < 256 * 16; x += 1024) {
-      const int c = x >> 8, rr = x & 255;
-      const int r = ck + rr;
-      if (rr < clen && c < nc && r >= c0) {
-        int gr = r < len0 ? base0 + r : base1 + (r - len0);
-        A[(size_t)(pcol0 + cg[c]) * ld + gr] -= Cc[rr * 16 + c];
+      for (int e = 0; e < 4; e++)
+        Cc[(wave * 16 + ksub + 4 * e) * 16 + r16] = accU[e];
+      __syncthreads();
+      // coalesced global RMW per column
+      for (int x = tid; x < 256 * 16; x += 1024) {
+        const int c = x >> 8, rr = x & 255;
+        const int r = ck + rr;
+        if (rr < clen && c < nc && r >= c0)
+          A[(size_t)(pcol0 + cg[c]) * ld + rm.global_row(r)] -=
+              Cc[rr * 16 + c];
       }
+      __syncthreads();
     }
-    __syncthreads();
-  }
-}
-
-__global__ void __launch_bounds__(1024) k_qr_panel_mw(
-    double* A, int ld, int pcol0,  // panel base column (global)
-    int base0, int len0, int base1, int len1,  // reflector row segments
-    int pc,     // total columns from pcol0 (factor + apply targets)
-    int fcols,  // columns to FACTOR (<=128)
-    int W,      // sub-panel width (8|16)
-    double* tau, double* T16s,  // T16s: 16x16 per sub-panel scratch
-    int* cnt, int nwg, int nA, int amode, int look,
-    unsigned long long* dbg) {
-  // Producer/consumer panel pipeline (no grid barriers):
-  //  - WG 0 factors 16-column sub-panels in LDS (one barrier per column,
-  //    piggybacked norms, deferred scaling), builds T16 with a parallel
-  //    G = V^T V, then PUBLISHES the sub-panel (agent release + counter).
-  //  - helper pool A (<=7 WGs) applies each published block reflector to
-  //    the remaining FACTOR columns and acks; WG 0 only stages sub-panel
-  //    s+1 after ack(s), so the factor chain never waits on the trailing
-  //    matrix.
-  //  - pool B (the rest) streams the same applies over the trailing
-  //    columns asynchronously, in publication order (each column has a
-  //    fixed owner, so per-column apply order is the program order).
-  // Memory protocol per MI355X_MICROARCH.md "Workgroup dispatch": plain
-  // stores -> release fence + vmcnt(0) asm -> relaxed counter; consumers
-  // poll relaxed, acquire-fence once, then plain loads.
-  __shared__ double sp[QR_LDS_DOUBLES];  // sub-panel / V image
-  __shared__ double red[16];             // norm partials (staging)
-  __shared__ double bcs[3 * 16];         // per-col {vd, beta, tfac}
-  __shared__ double tl[16];              // per-col tau (LDS copy)
-  __shared__ double wy[2 * 64];          // dots + y for 4 columns
-  __shared__ double gt[512];             // G (16x16) + local T (16x16)
-  const int rows = len0 + len1;
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int wg = blockIdx.x;
-  const int ns = (fcols + W - 1) / W;
-  const int nB = nwg - 1 - nA;
-
-  if (wg == 0) {
-    for (int si = 0; si < ns; si++) {
-      const int c0 = si * W;
-      const int w = min(W, fcols - c0);
-      double* T16 = T16s + (size_t)si * 256;
-      unsigned long long t0 = dbg ? __builtin_amdgcn_s_memrealtime() : 0;
-      if (dbg && tid == 0) {
-        unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        dbg[0] += t1 - t0;
-        t0 = t1;
-      }
-      // ---- stage sub-panel columns into LDS (+ first column's norm) ----
-      double acc0 = 0;
-      for (int q = 0; q < w; q++) {
-        const double* A0 = A + (size_t)(pcol0 + c0 + q) * ld + base0;
-        const double* A1 = A + (size_t)(pcol0 + c0 + q) * ld + base1 - len0;
-        double* spq = sp + (size_t)q * rows;
-        for (int r = tid; r < len0; r += 1024) {
-          double v = A0[r];
-          spq[r] = v;
-          if (q == 0 && r > c0) acc0 += v * v;
-        }
-        for (int r = len0 + tid; r < rows; r += 1024) {
-          double v = A1[r];
-          spq[r] = v;
-          if (q == 0) acc0 += v * v;
-        }
-      }
-      for (int sh = 32; sh > 0; sh >>= 1) acc0 += __shfl_down(acc0, sh);
-      if (lane == 0) red[wave] = acc0;
-      __syncthreads();
-      if (tid == 0) {
-        double nrm2 = 0;
-        for (int v = 0; v < 16; v++) nrm2 += red[v];
-        double alpha = sp[c0];
-        double beta = alpha, vd = 1.0, tfac = 0.0, tj = 0.0;
-        if (nrm2 != 0.0) {
-          beta = -copysign(sqrt(alpha * alpha + nrm2), alpha);
-          vd = alpha - beta;
-          tj = (beta - alpha) / beta;
-          tfac = tj / (vd * vd);
-        }
-        bcs[0] = vd;
-        bcs[1] = beta;
-        bcs[2] = tfac;
-        tl[0] = tj;
-        tau[c0] = tj;
-      }
-      __syncthreads();
-      if (dbg && tid == 0) {
-        unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        dbg[1] += t1 - t0;  // stage
-        t0 = t1;
-      }
-      // ---- factor: one barrier per column ----
-      for (int j = 0; j < w; j++) {
-        const int d = c0 + j;
-        const double vd = bcs[3 * j], tfac = bcs[3 * j + 2];
-        if (wave > j && wave < w) {
-          const double* col = sp + (size_t)j * rows;
-          double* cc = sp + (size_t)wave * rows;
-          double dot = (lane == 0) ? vd * cc[d] : 0.0;
-          double dot1 = 0.0;
-          for (int i = d + 1 + lane; i < rows; i += 128) dot += col[i] * cc[i];
-          for (int i = d + 65 + lane; i < rows; i += 128)
-            dot1 += col[i] * cc[i];
-          dot += dot1;
-          for (int sh = 32; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh);
-          dot = __shfl(dot, 0);
-          const double wj = tfac * dot;
-          if (lane == 0) cc[d] -= wj * vd;
-          double nacc = 0;
-          const bool mine = (wave == j + 1);
-          for (int i = d + 1 + lane; i < rows; i += 64) {
-            double nv = cc[i] - wj * col[i];
-            cc[i] = nv;
-            if (mine && i > d + 1) nacc += nv * nv;
-          }
-          if (mine) {
-            for (int sh = 32; sh > 0; sh >>= 1) nacc += __shfl_down(nacc, sh);
-            if (lane == 0) {
-              double alpha = cc[d + 1];
-              double beta = alpha, nvd = 1.0, tfac2 = 0.0, tj = 0.0;
-              if (nacc != 0.0) {
-                beta = -copysign(sqrt(alpha * alpha + nacc), alpha);
-                nvd = alpha - beta;
-                tj = (beta - alpha) / beta;
-                tfac2 = tj / (nvd * nvd);
-              }
-              bcs[3 * (j + 1)] = nvd;
-              bcs[3 * (j + 1) + 1] = beta;
-              bcs[3 * (j + 1) + 2] = tfac2;
-              tl[j + 1] = tj;
-              tau[c0 + j + 1] = tj;
-            }
-          }
-        }
-        __syncthreads();
-      }
-      if (dbg && tid == 0) {
-        unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        dbg[2] += t1 - t0;  // factor
-        t0 = t1;
-      }
-      // ---- scale pass ----
-      if (wave < w) {
-        const int d = c0 + wave;
-        double* col = sp + (size_t)wave * rows;
-        const double inv = 1.0 / bcs[3 * wave];
-        for (int i = d + 1 + lane; i < rows; i += 64) col[i] *= inv;
-        if (lane == 0) col[d] = bcs[3 * wave + 1];
-      }
-      __syncthreads();
-      // ---- write back ----
-      for (int q = 0; q < w; q++) {
-        double* A0 = A + (size_t)(pcol0 + c0 + q) * ld + base0;
-        double* A1 = A + (size_t)(pcol0 + c0 + q) * ld + base1 - len0;
-        const double* spq = sp + (size_t)q * rows;
-        for (int r = tid; r < len0; r += 1024) A0[r] = spq[r];
-        for (int r = len0 + tid; r < rows; r += 1024) A1[r] = spq[r];
-      }
-      __syncthreads();
-      if (dbg && tid == 0) {
-        unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        dbg[3] += t1 - t0;  // scale + writeback
-        t0 = t1;
-      }
-      // ---- G = V^T V: 64 units of 16 lanes over the (s<q) pairs ----
-      {
-        const int unit = wave * 4 + (lane >> 4), l16 = lane & 15;
-        const int npairs = w * (w - 1) / 2;
-        for (int idx = unit; idx < npairs; idx += 64) {
-          // decode idx -> (sq pair): q = row in triangle
-          int q = 1;
-          int rem = idx;
-          while (rem >= q) {
-            rem -= q;
-            q++;
-          }
-          int sc = rem;  // 0 <= sc < q
-          const int dq = c0 + q;
-          const double* cs = sp + (size_t)sc * rows;
-          const double* cq = sp + (size_t)q * rows;
-          // i >= dq > ds always: v_s = cs[i]; v_q = 1 at dq, cq[i] below
-          double dot = (l16 == 0) ? cs[dq] : 0.0;
-          double d1 = 0.0;
-          for (int i = dq + 1 + l16; i < rows; i += 32) dot += cs[i] * cq[i];
-          for (int i = dq + 17 + l16; i < rows; i += 32) d1 += cs[i] * cq[i];
-          dot += d1;
-          for (int sh = 8; sh > 0; sh >>= 1)
-            dot += __shfl_down(dot, sh, 16);
-          if (l16 == 0) gt[sc * 16 + q] = dot;  // G(sc, q)
-        }
-      }
-      __syncthreads();
-      if (wave == 0) {
-        double* Tl = gt + 256;
-        const double* G = gt;
-        for (int j = 0; j < w; j++) {
-          double tj = tl[j];
-          double sacc = 0;
-          if (lane < j) {
-            for (int q = lane; q < j; q++)
-              sacc += Tl[q * 16 + lane] * G[q * 16 + j];
-            sacc *= -tj;
-          }
-          if (lane < j) Tl[j * 16 + lane] = sacc;
-          if (lane == j) Tl[j * 16 + j] = tj;
-        }
-        if (lane < 16)
-          for (int j = 0; j < 16; j++)
-            T16[j * 16 + lane] =
-                (j < w && lane <= j) ? Tl[j * 16 + lane] : 0.0;
-      }
-      __syncthreads();
-      if (dbg && tid == 0) {
-        unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        dbg[4] += t1 - t0;  // G16 + T16
-        t0 = t1;
-      }
-      // ---- publish sub-panel si ----
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(&cnt[0], si + 1, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-      }
-      // ---- wait for pool A to finish sub-panel si-1 everywhere: its
-      // range [c0-W+2W, fcols) includes OUR self-apply window, and the
-      // si-1 reflectors must land on those columns before si's do. The
-      // factor of si overlapped pool A's si-1 pass, so this wait is the
-      // pipeline's only rendezvous. With qr_lookahead=0 the self-apply is
-      // off and the wait covers pool A through si instead. ----
-      if (tid == 0) {
-        while (__hip_atomic_load(&cnt[1], __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT) <
-               (si + (look ? 0 : 1)) * nA)
-          __builtin_amdgcn_s_sleep(2);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      }
-      __syncthreads();
-      // ---- self-apply this block to the NEXT sub-panel's columns (the
-      // V image is already in sp, minus the unit-lower masking) ----
-      for (int c = c0 + w; look && c < min(c0 + 2 * W, fcols); c += 4) {
-        const int nc = min(4, min(c0 + 2 * W, fcols) - c);
-        const int ci = lane >> 4, l16 = lane & 15;
-        if (ci < nc && wave < w) {
-          const int gcol = pcol0 + c + ci;
-          const int cloc = c0 + wave;
-          const double* v = sp + (size_t)wave * rows;
-          const double* A0 = A + (size_t)gcol * ld + base0;
-          const double* A1 = A + (size_t)gcol * ld + base1 - len0;
-          // raw sp has R above the diagonal: start at cloc, inject the
-          // unit diagonal by hand
-          double dot = (l16 == 0) ? A0[cloc] : 0.0;
-          double d1 = 0;
-          for (int r = cloc + 1 + l16; r < len0; r += 32)
-            dot += v[r] * A0[r];
-          for (int r = cloc + 17 + l16; r < len0; r += 32)
-            d1 += v[r] * A0[r];
-          for (int r = len0 + l16; r < rows; r += 32) dot += v[r] * A1[r];
-          for (int r = len0 + 16 + l16; r < rows; r += 32)
-            d1 += v[r] * A1[r];
-          dot += d1;
-          for (int sh = 8; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh, 16);
-          if (l16 == 0) wy[ci * 16 + wave] = dot;
-        }
-        __syncthreads();
-        if (tid < 16 * nc) {
-          const int q = tid & 15, cc2 = tid >> 4;
-          double sacc = 0;
-          for (int p2 = 0; p2 <= q; p2++)
-            sacc += T16[q * 16 + p2] * wy[cc2 * 16 + p2];
-          wy[64 + cc2 * 16 + q] = sacc;
-        }
-        __syncthreads();
-        {
-          const int cc2 = tid >> 8, t2 = tid & 255;
-          if (cc2 < nc) {
-            const int gcol = pcol0 + c + cc2;
-            double* A0 = A + (size_t)gcol * ld + base0;
-            double* A1 = A + (size_t)gcol * ld + base1 - len0;
-            const double* y = wy + 64 + cc2 * 16;
-            for (int r = c0 + t2; r < len0; r += 256) {
-              double sacc = 0;
-              for (int q = 0; q < w; q++) {
-                const int cloc = c0 + q;
-                double v = r < cloc ? 0.0
-                                    : (r == cloc ? 1.0
-                                                 : sp[(size_t)q * rows + r]);
-                sacc += v * y[q];
-              }
-              A0[r] -= sacc;
-            }
-            for (int r = len0 + t2; r < rows; r += 256) {
-              double sacc = 0;
-              for (int q = 0; q < w; q++)
-                sacc += sp[(size_t)q * rows + r] * y[q];
-              A1[r] -= sacc;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
-    return;
   }
 
-  // ---------------- helper workgroups ----------------
-  const bool poolA = wg <= nA;
-  for (int si = 0; si < ns; si++) {
-    const int c0 = si * W;
-    const int w = min(W, fcols - c0);
-    const double* T16 = T16s + (size_t)si * 256;
-    unsigned long long t0 =
-        (dbg && (wg == 1 || wg == nA + 1)) ? __builtin_amdgcn_s_memrealtime()
-                                           : 0;
-    if (tid == 0) {
-      while (__hip_atomic_load(&cnt[0], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT) < si + 1)
-        __builtin_amdgcn_s_sleep(2);
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-    const int dslot = (wg == 1) ? 5 : (wg == nA + 1 ? 8 : -1);
-    if (dbg && dslot >= 0 && tid == 0) {
-      unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-      dbg[dslot] += t1 - t0;  // publish poll wait
-      t0 = t1;
-    }
-    if (!amode || poolA) {
-      // cache the scaled V image (unit-lower) in LDS (VALU apply path;
-      // the MFMA path streams V chunks itself)
-      for (int q = 0; q < w; q++) {
-        const int gcol = pcol0 + c0 + q, cloc = c0 + q;
-        const double* A0 = A + (size_t)gcol * ld + base0;
-        const double* A1 = A + (size_t)gcol * ld + base1 - len0;
-        double* spq = sp + (size_t)q * rows;
-        for (int r = tid; r < len0; r += 1024)
-          spq[r] = r < cloc ? 0.0 : (r == cloc ? 1.0 : A0[r]);
-        for (int r = len0 + tid; r < rows; r += 1024) spq[r] = A1[r];
-      }
-    }
-    __syncthreads();
-    if (dbg && dslot >= 0 && tid == 0) {
-      unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-      dbg[dslot + 1] += t1 - t0;  // V image build
-      t0 = t1;
-    }
-    // apply (I - V T V^T)^T to 4-column groups of my column set
-    auto apply4 = [&](int cg[4], int nc) {
-      const int ci = lane >> 4, l16 = lane & 15;  // unit = (q=wave, ci)
-      // wave >= w has no reflector: with W=8 its sp + wave * rows lies
-      // past the V image (past sp itself at 2304 rows)
-      if (ci < nc && wave < w) {
-        const int gcol = pcol0 + cg[ci];
-        const int cloc = c0 + wave;
-        const double* v = sp + (size_t)wave * rows;
-        const double* A0 = A + (size_t)gcol * ld + base0;
-        const double* A1 = A + (size_t)gcol * ld + base1 - len0;
-        double d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-        for (int r = cloc + l16; r < len0; r += 64) d0 += v[r] * A0[r];
-        for (int r = cloc + 16 + l16; r < len0; r += 64) d1 += v[r] * A0[r];
-        for (int r = cloc + 32 + l16; r < len0; r += 64) d2 += v[r] * A0[r];
-        for (int r = cloc + 48 + l16; r < len0; r += 64) d3 += v[r] * A0[r];
-        for (int r = len0 + l16; r < rows; r += 64) d0 += v[r] * A1[r];
-        for (int r = len0 + 16 + l16; r < rows; r += 64) d1 += v[r] * A1[r];
-        for (int r = len0 + 32 + l16; r < rows; r += 64) d2 += v[r] * A1[r];
-        for (int r = len0 + 48 + l16; r < rows; r += 64) d3 += v[r] * A1[r];
-        double dot = (d0 + d1) + (d2 + d3);
-        for (int sh = 8; sh > 0; sh >>= 1) dot += __shfl_down(dot, sh, 16);
-        if (l16 == 0) wy[ci * 16 + wave] = dot;
-      }
-      __syncthreads();
-      if (tid < 16 * nc) {
-        const int q = tid & 15, c = tid >> 4;
-        double sacc = 0;
-        for (int p2 = 0; p2 <= q; p2++)
-          sacc += T16[q * 16 + p2] * wy[c * 16 + p2];
-        wy[64 + c * 16 + q] = sacc;
-      }
-      __syncthreads();
-      {
-        const int c = tid >> 8, t2 = tid & 255;  // 4 cols x 256 threads
-        if (c < nc) {
-          const int gcol = pcol0 + cg[c];
-          double* A0 = A + (size_t)gcol * ld + base0;
-          double* A1 = A + (size_t)gcol * ld + base1 - len0;
-          const double* y = wy + 64 + c * 16;
-          for (int r = c0 + t2; r < len0; r += 256) {
-            double sacc = 0;
-            for (int q = 0; q < w; q++) sacc += sp[(size_t)q * rows + r] * y[q];
-            A0[r] -= sacc;
-          }
-          for (int r = len0 + t2; r < rows; r += 256) {
-            double sacc = 0;
-            for (int q = 0; q < w; q++) sacc += sp[(size_t)q * rows + r] * y[q];
-            A1[r] -= sacc;
-          }
-        }
-      }
-      __syncthreads();
-    };
-    // Column ownership must be ABSOLUTE (c mod stride == phase), not
-    // relative to cbeg: cbeg advances with the sub-panel, and a column
-    // whose owner changed between sub-panels would receive reflector
-    // applies from two helpers with NO mutual ordering (measured: rare
-    // mid-panel corruption, first bad column inside pool A's range).
-    auto apply_range = [&](int cbeg, int cend, int stride, int phase,
-                           bool mfma) {
-      int first = cbeg + (((phase - cbeg) % stride) + stride) % stride;
-      if (amode && mfma) {
-        int cg[16];
-        int nc = 0;
-        for (int c = first; c < cend; c += stride) {
-          cg[nc++] = c;
-          if (nc == 16) {
-            qr_apply_mfma16(A, ld, pcol0, base0, len0, base1, rows, c0, w,
-                            T16, cg, 16, sp, wy, tid, wave, lane);
-            nc = 0;
-          }
-        }
-        if (nc)
-          qr_apply_mfma16(A, ld, pcol0, base0, len0, base1, rows, c0, w,
-                          T16, cg, nc, sp, wy, tid, wave, lane);
-        return;
-      }
-      int cg[4];
+  // Apply the block reflector to this workgroup's share of the panel
+  // columns [cbeg, cend): 16 at a time by MFMA, or 4 at a time by the VALU
+  // phases on the V image.
+  // Column ownership must be ABSOLUTE (c mod stride == phase), not
+  // relative to cbeg: cbeg advances with the sub-panel, and a column whose
+  // owner changed between sub-panels would receive reflector applies from
+  // two helpers with NO mutual ordering (measured: rare mid-panel
+  // corruption, first bad column inside pool A's range).
+  QR_DEV void apply_range(int cbeg, int cend, int stride, int phase,
+                          bool mfma) {
+    int first = cbeg + (((phase - cbeg) % stride) + stride) % stride;
+    if (amode && mfma) {
+      int cg[16];
       int nc = 0;
       for (int c = first; c < cend; c += stride) {
         cg[nc++] = c;
-        if (nc == 4) {
-          apply4(cg, 4);
+        if (nc == 16) {
+          apply_mfma16(cg, 16);
           nc = 0;
         }
       }
-      if (nc) apply4(cg, nc);
+      if (nc) apply_mfma16(cg, nc);
+      return;
+    }
+    // wave >= w has no reflector: with W=8 its sp + wave * rows lies past
+    // the V image (past sp itself at 2304 rows)
+    auto apply4 = [&](const int* cg, int nc) {
+      const int ci = lane >> 4;
+      if (ci < nc && wave < w) dots_image(pcol0 + cg[ci], ci);
+      apply_finish<false>(nc, [=](int i) { return cg[i]; });
     };
-    if (poolA) {
-      // small within-panel groups: the latency-optimized VALU units win;
-      // the MFMA path pays per-256-row chunk staging regardless of nc
-      apply_range(look ? min(c0 + 2 * W, fcols) : c0 + w, fcols, nA,
-                  wg - 1, false);
-      __syncthreads();
-      if (dbg && dslot >= 0 && tid == 0)
-        dbg[dslot + 2] += __builtin_amdgcn_s_memrealtime() - t0;  // apply
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_fetch_add(&cnt[1], 1, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+    int cg[4];
+    int nc = 0;
+    for (int c = first; c < cend; c += stride) {
+      cg[nc++] = c;
+      if (nc == 4) {
+        apply4(cg, 4);
+        nc = 0;
       }
-      if (nB == 0)  // no pool B: pool A also covers the trailing columns
-        apply_range(fcols, pc, nA, wg - 1, true);
-    } else {
-      apply_range(fcols, pc, nB, wg - 1 - nA, true);
-      if (dbg && dslot >= 0 && tid == 0)
-        dbg[dslot + 2] += __builtin_amdgcn_s_memrealtime() - t0;  // apply
+    }
+    if (nc) apply4(cg, nc);
+  }
+
+  QR_DEV void run_helper(int wg) {
+    const int nB = nwg - 1 - nA;
+    const bool poolA = wg <= nA;
+    // the first helper of each pool keeps the timers
+    const int dslot = (wg == 1) ? 5 : (wg == nA + 1 ? 8 : -1);
+    for (int si = 0; si < subpanels(); si++) {
+      select(si);
+      QrTimer tm((dslot >= 0 && tid == 0) ? dbg : nullptr);
+      if (tid == 0) qr_wait_ge(&cnt[0], si + 1);
+      __syncthreads();
+      tm.lap(dslot);  // publish poll wait
+      // the VALU apply reads V from LDS; the MFMA path streams V chunks
+      // itself
+      if (!amode || poolA) build_v_image();
+      __syncthreads();
+      tm.lap(dslot + 1);  // V image build
+      if (poolA) {
+        // small within-panel groups: the latency-optimized VALU units win;
+        // the MFMA path pays per-256-row chunk staging regardless of nc
+        apply_range(look ? min(c0 + 2 * W, fcols) : c0 + w, fcols, nA,
+                    wg - 1, false);
+        __syncthreads();
+        tm.lap(dslot + 2);  // apply
+        if (tid == 0) qr_signal_add(&cnt[1]);
+        if (nB == 0)  // no pool B: pool A also covers the trailing columns
+          apply_range(fcols, pc, nA, wg - 1, true);
+      } else {
+        apply_range(fcols, pc, nB, wg - 1 - nA, true);
+        tm.lap(dslot + 2);  // apply
+      }
     }
   }
+};
+
+__global__ void __launch_bounds__(1024) k_qr_panel_mw(QrPanelArgs args) {
+  __shared__ double sp[QR_LDS_DOUBLES];
+  __shared__ double red[16];
+  __shared__ double bcs[3 * 16];
+  __shared__ double tl[16];
+  __shared__ double wy[2 * 64];
+  __shared__ double gt[512];
+  const int tid = threadIdx.x;
+  QrPanel p{args, sp, red, bcs, tl, wy, gt, tid, tid >> 6, tid & 63,
+            args.rm.len0, args.rm.rows(), 0, 0, nullptr};
+  if (blockIdx.x == 0)
+    p.run_wg0();
+  else
+    p.run_helper(blockIdx.x);
 }
+
+#undef QR_DEV
 
 }  // namespace
 
@@ -1046,9 +1097,10 @@ struct QrPanelCfg {
     amode = kind == "valu" ? 0 : 1;
   }
   // WG 0 factors, so there is at least one helper, and pool A is never
-  // empty: nobody else applies a sub-panel to the panel's own columns.
+  // empty: nobody else applies a sub-panel to the panel's own columns. The
+  // workgroups wait on each other, so no more than can be resident at once.
   void clamp() {
-    nwg = std::max(2, nwg);
+    nwg = std::min(QR_PANEL_MAX_WGS, std::max(2, nwg));
     nA = std::min(nwg - 1, std::max(1, nA));
   }
 };
@@ -1065,6 +1117,63 @@ static QrPanelCfg qr_cfg_from_params() {
   return c;
 }
 
+// Row map and sub-panel width of the pc-column panel at (p, p) of an m-row
+// tile: a dense panel, or with ts_split > 0 the triangular top (pc rows of
+// R) plus the dense bottom. W = 0: too many rows for the panel kernel.
+struct QrPanelGeom {
+  QrRowMap rm;
+  int W;
+};
+static QrPanelGeom qr_panel_geom(int m, int p, int pc, int ts_split) {
+  QrRowMap rm{p, m - p, 0, 0};
+  if (ts_split > 0)
+    rm = {p, std::min(pc, ts_split - p), ts_split, m - ts_split};
+  const int rows = rm.rows();
+  const int W = rows <= QR_MAX_ROWS_W16 ? 16 : (rows <= QR_MAX_ROWS_W8 ? 8 : 0);
+  return {rm, W};
+}
+
+// One panel-kernel launch: factor the pc columns at column p of A and apply
+// them to the apply_cols columns from p on (the panel's own included).
+static void launch_qr_panel(GpuTaskCtx& g, const QrPanelCfg& cfg, double* A,
+                            int ld, int p, const QrPanelGeom& geo,
+                            int apply_cols, int pc, double* tau,
+                            unsigned long long* dbg) {
+  double* T16s =
+      qr_scratch(g, QR_SLOT_T16S, (size_t)QR_MAX_SUBPANELS * 256 * 8);
+  int* cnt = (int*)qr_scratch(g, QR_SLOT_CNT, 256);
+  PA_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int), g.stream));
+  const QrPanelArgs a{A, ld, p, geo.rm, /*pc=*/apply_cols, /*fcols=*/pc,
+                      geo.W, tau + p, T16s, cnt, cfg.nwg, cfg.nA, cfg.amode,
+                      cfg.look, dbg};
+  hipLaunchKernelGGL(k_qr_panel_mw, dim3(cfg.nwg), dim3(1024), 0, g.stream,
+                     a);
+}
+
+// T128 of the factored pc-column panel at (p, p) from G = V^T V, then
+// larfb_gemm on the `rest` columns to its right.
+static void qr_larfb_trailing(GpuTaskCtx& g, double* A, int m, int ld, int p,
+                              int pc, int rest, const double* tau) {
+  rocblas_handle h = blas_handle(g);
+  const double one = 1.0, zero = 0.0;
+  const int prows = m - p;
+  double* panel = A + (size_t)p * ld + p;
+  double* V = qr_scratch(g, QR_SLOT_V, (size_t)prows * 128 * 8);
+  double* G = qr_scratch(g, QR_SLOT_G128, (size_t)128 * 128 * 8);
+  hipLaunchKernelGGL(k_unitlow, grid1d(prows * pc), dim3(256), 0, g.stream,
+                     V, panel, prows, pc, ld, prows);
+  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                         rocblas_operation_none, pc, pc, prows, &one, V,
+                         prows, V, prows, &zero, G,
+                         pc) == rocblas_status_success);
+  double* T128 = qr_scratch(g, QR_SLOT_T128, (size_t)128 * 128 * 8);
+  PA_HIP_CHECK(hipMemsetAsync(T128, 0, (size_t)pc * pc * 8, g.stream));
+  hipLaunchKernelGGL(k_larft_diag, dim3(1), dim3(128), 0, g.stream, G, pc,
+                     tau + p, T128, pc, pc);
+  larfb_gemm(g, prows, rest, pc, panel, ld, T128, pc,
+             A + (size_t)(p + pc) * ld + p, ld, QR_SLOT_LARFB);
+}
+
 // Full tile/stacked-panel QR: factor 128-wide panels with the multi-WG
 // panel kernel (k_geqr2 single-WG fallback for oversized rows), apply to
 // the trailing columns with gemm-larfb, then build the full k x k T.
@@ -1072,85 +1181,37 @@ static QrPanelCfg qr_cfg_from_params() {
 // the panel kernel then skips the structurally-zero block below R's
 // diagonal band, capping active rows at 128 + (m - ts_split).
 static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
-                           double* T, int ldt, int slot0, int ts_split,
+                           double* T, int ldt, int ts_split,
                            const QrPanelCfg& cfg) {
   rocblas_handle h = blas_handle(g);
-  double* tau = qr_scratch(g, slot0, (size_t)k * 8);
-  double* T16s = qr_scratch(g, slot0 + 9, (size_t)QR_MAX_SUBPANELS * 256 * 8);
-  int* cnt = (int*)qr_scratch(g, slot0 + 10, 256);
-  const int nwg = cfg.nwg, nA = cfg.nA;
+  double* tau = qr_scratch(g, QR_SLOT_TAU, (size_t)k * 8);
   const double one = 1.0, zero = 0.0, mone = -1.0;
   PA_HIP_CHECK(hipMemsetAsync(T, 0, (size_t)ldt * k * 8, g.stream));
   for (int p = 0; p < k; p += 128) {
-    int pc = std::min(128, k - p);
-    double* panel = A + (size_t)p * ld + p;
-    int prows = m - p;
-    // row segments: dense panel, or triangular-top + dense-bottom
-    int base0 = p, len0 = prows, base1 = 0, len1 = 0;
-    if (ts_split > 0) {
-      len0 = std::min(pc, ts_split - p);
-      base1 = ts_split;
-      len1 = m - ts_split;
-    }
-    int rows = len0 + len1;
-    int W = rows <= QR_MAX_ROWS_W16 ? 16 : (rows <= QR_MAX_ROWS_W8 ? 8 : 0);
-    if (W) {
+    const int pc = std::min(128, k - p);
+    const int rest = k - p - pc;
+    const QrPanelGeom geo = qr_panel_geom(m, p, pc, ts_split);
+    if (geo.W) {
       // qr_apply=kernel (default): the panel kernel both factors and
       // applies to ALL remaining tile columns (no per-panel dgemms).
       // qr_apply=gemm: the kernel applies within the 128 panel columns
       // only; the trailing matrix goes through T128 + larfb dgemms at
       // Tensile rates (A/B: the in-kernel apply units are latency-bound,
       // profiles/qr_round2.md).
-      int rest = k - p - pc;
-      int apply_cols = cfg.apply_gemm ? pc : k - p;
-      PA_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int), g.stream));
-      hipLaunchKernelGGL(k_qr_panel_mw, dim3(nwg), dim3(1024), 0, g.stream,
-                         A, ld, p, base0, len0, base1, len1, apply_cols, pc,
-                         W, tau + p, T16s, cnt, nwg, nA, cfg.amode, cfg.look,
-                         (unsigned long long*)nullptr);
-      if (cfg.apply_gemm && rest > 0) {
-        double* V = qr_scratch(g, slot0 + 1, (size_t)prows * 128 * 8);
-        double* G = qr_scratch(g, slot0 + 2, (size_t)128 * 128 * 8);
-        hipLaunchKernelGGL(k_unitlow, grid1d(prows * pc), dim3(256), 0,
-                           g.stream, V, panel, prows, pc, ld, prows);
-        PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                               rocblas_operation_none, pc, pc, prows, &one,
-                               V, prows, V, prows, &zero, G,
-                               pc) == rocblas_status_success);
-        double* T128 = qr_scratch(g, slot0 + 3, (size_t)128 * 128 * 8);
-        PA_HIP_CHECK(hipMemsetAsync(T128, 0, (size_t)pc * pc * 8, g.stream));
-        hipLaunchKernelGGL(k_larft_diag, dim3(1), dim3(128), 0, g.stream, G,
-                           pc, tau + p, T128, pc, pc);
-        larfb_gemm(g, prows, rest, pc, panel, ld, T128, pc,
-                   A + (size_t)(p + pc) * ld + p, ld, slot0 + 4);
-      }
+      launch_qr_panel(g, cfg, A, ld, p, geo, cfg.apply_gemm ? pc : k - p, pc,
+                      tau, nullptr);
+      if (cfg.apply_gemm && rest > 0)
+        qr_larfb_trailing(g, A, m, ld, p, pc, rest, tau);
       continue;
     }
-    hipLaunchKernelGGL(k_geqr2, dim3(1), dim3(1024), 0, g.stream, panel,
-                       prows, pc, ld, tau + p);
-    int rest = k - p - pc;
-    if (rest > 0) {
-      // T128 for this panel from G128 = V^T V
-      double* V = qr_scratch(g, slot0 + 1, (size_t)prows * 128 * 8);
-      double* G = qr_scratch(g, slot0 + 2, (size_t)128 * 128 * 8);
-      hipLaunchKernelGGL(k_unitlow, grid1d(prows * pc), dim3(256), 0,
-                         g.stream, V, panel, prows, pc, ld, prows);
-      PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                             rocblas_operation_none, pc, pc, prows, &one, V,
-                             prows, V, prows, &zero, G,
-                             pc) == rocblas_status_success);
-      double* T128 = qr_scratch(g, slot0 + 3, (size_t)128 * 128 * 8);
-      PA_HIP_CHECK(hipMemsetAsync(T128, 0, (size_t)pc * pc * 8, g.stream));
-      hipLaunchKernelGGL(k_larft_diag, dim3(1), dim3(128), 0, g.stream, G,
-                         pc, tau + p, T128, pc, pc);
-      larfb_gemm(g, prows, rest, pc, panel, ld, T128, pc,
-                 A + (size_t)(p + pc) * ld + p, ld, slot0 + 4);
-    }
+    hipLaunchKernelGGL(k_geqr2, dim3(1), dim3(1024), 0, g.stream,
+                       A + (size_t)p * ld + p, m - p, pc, ld, tau + p);
+    if (rest > 0) qr_larfb_trailing(g, A, m, ld, p, pc, rest, tau);
   }
   // Full T: G = V^T V over all k columns, diag blocks in one launch,
   // off-diagonal blocks by blocked combine (T[0:J,blk] = -T·G·T_blk).
-  double* V = qr_scratch(g, slot0 + 1, (size_t)m * k * 8);
-  double* G = qr_scratch(g, slot0 + 7, (size_t)k * k * 8);
+  double* V = qr_scratch(g, QR_SLOT_V, (size_t)m * k * 8);
+  double* G = qr_scratch(g, QR_SLOT_G, (size_t)k * k * 8);
   hipLaunchKernelGGL(k_unitlow, grid1d(m * k), dim3(256), 0, g.stream, V, A,
                      m, k, ld, m);
   PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
@@ -1158,7 +1219,7 @@ static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
                          &zero, G, k) == rocblas_status_success);
   hipLaunchKernelGGL(k_larft_diag, dim3((k + 127) / 128), dim3(128), 0,
                      g.stream, G, k, tau, T, ldt, k);
-  double* X = qr_scratch(g, slot0 + 8, (size_t)k * 128 * 8);
+  double* X = qr_scratch(g, QR_SLOT_X, (size_t)k * 128 * 8);
   for (int b = 128; b < k; b += 128) {
     int bc2 = std::min(128, k - b);
     // X = T(0:b,0:b) * G(0:b, b:b+bc)
@@ -1177,7 +1238,7 @@ static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
 // of it are cleared first).
 static void qr_factor_rocsolver(GpuTaskCtx& g, double* A, int m, int k,
                                 int ld, double* T, int ldt, size_t t_bytes) {
-  double* tau = qr_scratch(g, 0, (size_t)k * 8);
+  double* tau = qr_scratch(g, QR_SLOT_TAU, (size_t)k * 8);
   rocblas_handle h = blas_handle(g);
   PA_HIP_CHECK(hipMemsetAsync(T, 0, t_bytes, g.stream));
   PA_CHECK(rocsolver_dgeqrf(h, m, k, A, ld, tau) == rocblas_status_success);
@@ -1193,57 +1254,17 @@ static void gpu_geqrt(Task& t, GpuTaskCtx& g) {
   static const bool use_rocsolver =
       param_str("chore_qr", "hand") == "rocsolver";
   if (!use_rocsolver) {
-    qr_factor_hand(g, A, a.n, a.n, a.ld, T, a.ld, 0, 0, qr_cfg_from_params());
+    qr_factor_hand(g, A, a.n, a.n, a.ld, T, a.ld, 0, qr_cfg_from_params());
     return;
   }
   qr_factor_rocsolver(g, A, a.n, a.n, a.ld, T, a.ld, t.flows[1].data->bytes);
-}
-
-__global__ void k_unitlow(double* V, const double* A, int m, int k, int lda,
-                          int ldv) {
-  // V = unit-lower copy of A's reflector block (zeros above, 1 on diag)
-  int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  int total = m * k;
-  for (; idx < total; idx += gridDim.x * blockDim.x) {
-    int c = idx / m, r = idx - c * m;
-    double v = r < c ? 0.0 : (r == c ? 1.0 : A[(size_t)c * lda + r]);
-    V[(size_t)c * ldv + r] = v;
-  }
-}
-
-// C = (I - V T V^T)^T C via three full-rate dgemms (rocSOLVER's dlarfb
-// decomposes into micro-kernels at these sizes: profiles/RESULTS.md).
-// V: m x k reflectors (unit-lower inside A-storage), T: k x k upper
-// (zeros elsewhere), C: m x n. Scratch: V expanded + W (k x n).
-static void larfb_gemm(GpuTaskCtx& g, int m, int n, int k, const double* A,
-                       int lda, const double* T, int ldt, double* C, int ldc,
-                       int scratch_slot) {
-  rocblas_handle h = blas_handle(g);
-  double* V = qr_scratch(g, scratch_slot, (size_t)m * k * 8);
-  double* W = qr_scratch(g, scratch_slot + 1, (size_t)k * n * 8);
-  hipLaunchKernelGGL(k_unitlow, grid1d(m * k), dim3(256), 0, g.stream, V, A,
-                     m, k, lda, m);
-  const double one = 1.0, zero = 0.0, mone = -1.0;
-  // W = V^T C
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, k, n, m, &one, V, m, C, ldc,
-                         &zero, W, k) == rocblas_status_success);
-  // W = T^T W  (T upper-triangular, stored dense with zero lower)
-  double* W2 = qr_scratch(g, scratch_slot + 2, (size_t)k * n * 8);
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, k, n, k, &one, T, ldt, W, k,
-                         &zero, W2, k) == rocblas_status_success);
-  // C -= V W2
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
-                         m, n, k, &mone, V, m, W2, k, &one, C,
-                         ldc) == rocblas_status_success);
 }
 
 static void gpu_unmqr(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   larfb_gemm(g, a.m, a.n, a.m, (const double*)t.dev_ptr[0], a.ld,
              (const double*)t.dev_ptr[1], a.ld, (double*)t.dev_ptr[2], a.ld,
-             4);
+             QR_SLOT_LARFB);
 }
 
 static void gpu_tsqrt(Task& t, GpuTaskCtx& g) {
@@ -1258,7 +1279,7 @@ static void gpu_tsqrt(Task& t, GpuTaskCtx& g) {
   static const bool use_rocsolver =
       param_str("chore_qr", "hand") == "rocsolver";
   if (!use_rocsolver) {
-    qr_factor_hand(g, V2, 2 * nb, nb, 2 * nb, T1, ld, 0, /*ts_split=*/nb,
+    qr_factor_hand(g, V2, 2 * nb, nb, 2 * nb, T1, ld, /*ts_split=*/nb,
                    qr_cfg_from_params());
   } else {
     qr_factor_rocsolver(g, V2, 2 * nb, nb, 2 * nb, T1, ld,
@@ -1275,27 +1296,16 @@ static void gpu_tsmqr(Task& t, GpuTaskCtx& g) {
   double* T1 = (double*)t.dev_ptr[1];
   double* Ckn = (double*)t.dev_ptr[2];
   double* Cmn = (double*)t.dev_ptr[3];
-  double* S = qr_scratch(g, 1, (size_t)2 * nb * cols * 8);
+  double* S = qr_scratch(g, QR_SLOT_V, (size_t)2 * nb * cols * 8);
   hipLaunchKernelGGL(k_stack, grid1d(nb * cols), dim3(256), 0, g.stream, S,
                      Ckn, Cmn, nb, cols, ld);
-  larfb_gemm(g, 2 * nb, cols, nb, V2, 2 * nb, T1, ld, S, 2 * nb, 8);
+  larfb_gemm(g, 2 * nb, cols, nb, V2, 2 * nb, T1, ld, S, 2 * nb,
+             QR_SLOT_LARFB_TS);
   hipLaunchKernelGGL(k_unstack, grid1d(nb * cols), dim3(256), 0, g.stream, S,
                      Ckn, Cmn, nb, cols, ld);
 }
 
 // ------------------------------------------------------------ task classes
-static TaskClass make_qr_tc(const char* name, void (*cpu)(Task&),
-                            void (*gpu)(Task&, GpuTaskCtx&), int id) {
-  Profiler::inst().register_class(id, name);
-  TaskClass tc;
-  tc.name = name;
-  tc.kind = TaskKind::GPU;
-  tc.cpu_hook = cpu;
-  tc.gpu_hook = gpu;
-  tc.id = id;
-  return tc;
-}
-
 TaskClass& tc_geqrt() {
   // rocSOLVER panel factorizations host-sync internally: run them on
   // worker threads (gpu_blocking) so the manager keeps the trailing
@@ -1303,7 +1313,7 @@ TaskClass& tc_geqrt() {
   // panel kernel), so it pipelines through the manager like any chore.
   // PARSEC_MCA_qr_blocking_panels=0 restores manager execution.
   static TaskClass tc = [] {
-    TaskClass c = make_qr_tc("geqrt", cpu_geqrt, gpu_geqrt, 10);
+    TaskClass c = make_tc("geqrt", TaskKind::GPU, cpu_geqrt, gpu_geqrt, 10);
     bool rocs = param_str("chore_qr", "hand") == "rocsolver";
     c.gpu_blocking = rocs && param_int("qr_blocking_panels", 1) != 0;
     return c;
@@ -1311,12 +1321,13 @@ TaskClass& tc_geqrt() {
   return tc;
 }
 TaskClass& tc_unmqr() {
-  static TaskClass tc = make_qr_tc("unmqr", cpu_unmqr, gpu_unmqr, 11);
+  static TaskClass tc =
+      make_tc("unmqr", TaskKind::GPU, cpu_unmqr, gpu_unmqr, 11);
   return tc;
 }
 TaskClass& tc_tsqrt() {
   static TaskClass tc = [] {
-    TaskClass c = make_qr_tc("tsqrt", cpu_tsqrt, gpu_tsqrt, 12);
+    TaskClass c = make_tc("tsqrt", TaskKind::GPU, cpu_tsqrt, gpu_tsqrt, 12);
     bool rocs = param_str("chore_qr", "hand") == "rocsolver";
     c.gpu_blocking = rocs && param_int("qr_blocking_panels", 1) != 0;
     return c;
@@ -1324,7 +1335,8 @@ TaskClass& tc_tsqrt() {
   return tc;
 }
 TaskClass& tc_tsmqr() {
-  static TaskClass tc = make_qr_tc("tsmqr", cpu_tsmqr, gpu_tsmqr, 13);
+  static TaskClass tc =
+      make_tc("tsmqr", TaskKind::GPU, cpu_tsmqr, gpu_tsmqr, 13);
   return tc;
 }
 
@@ -1445,66 +1457,43 @@ void insert_geqrf(Dtd& tp, TiledMatrix& A) {
   }
 }
 
-// Standalone micro-benchmark of the TS/tile panel factorization path:
-// mode 0 = full qr_factor_hand, 1 = panel kernels only, 2 = rocsolver
-// dgeqrf. Returns seconds for `iters` factorizations of an m x k tile.
+// Standalone micro-benchmark of the TS/tile panel factorization path, by
+// QrBenchMode. Returns seconds for `iters` factorizations of an m x k tile.
 double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
-  double *dA, *dT;
-  PA_HIP_CHECK(hipMalloc(&dA, (size_t)m * k * 8));
-  PA_HIP_CHECK(hipMalloc(&dT, (size_t)k * k * 8));
+  PA_CHECK(mode == QR_BENCH_FULL || mode == QR_BENCH_PANELS ||
+               mode == QR_BENCH_ROCSOLVER || mode == QR_BENCH_PANELS_TIMED,
+           "bench_qr_factor: mode %d", mode);
+  DevArray dA((size_t)m * k), dT((size_t)k * k);
+  DevArray<unsigned long long> dbg(16);
+  PA_HIP_CHECK(hipMemset(dbg.p, 0, dbg.bytes));
+  const bool timed = mode == QR_BENCH_PANELS_TIMED;
   hipStream_t s;
   PA_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   std::vector<std::pair<void*, size_t>> defer;
   GpuTaskCtx g{s, 0, nullptr, &defer};
-  double* tau = qr_scratch(g, 0, (size_t)k * 8);
-  double* T16s = qr_scratch(g, 9, (size_t)QR_MAX_SUBPANELS * 256 * 8);
-  int* cnt = (int*)qr_scratch(g, 10, 256);
-  unsigned long long* dbg = nullptr;
-  if (mode == 5) {
-    PA_HIP_CHECK(hipMalloc(&dbg, 16 * 8));
-    PA_HIP_CHECK(hipMemset(dbg, 0, 16 * 8));
-    mode = 1;
-  }
+  double* tau = qr_scratch(g, QR_SLOT_TAU, (size_t)k * 8);
   const QrPanelCfg cfg = qr_cfg_from_params();
-  const int nwg = cfg.nwg, nA = cfg.nA;
-  auto run = [&] {
-    hipLaunchKernelGGL(k_qr_fill, dim3(2048), dim3(256), 0, s, dA,
+  double dt = time_launches(iters, [&] {
+    hipLaunchKernelGGL(k_qr_fill, dim3(2048), dim3(256), 0, s, dA.p,
                        (size_t)m * k, 7);
-    if (mode == 0) {
-      qr_factor_hand(g, dA, m, k, m, dT, k, 0, ts_split, cfg);
-    } else if (mode == 1 || mode >= 16) {
-      for (int p = 0; p < k; p += 128) {
-        int pc = std::min(128, k - p);
-        int base0 = p, len0 = m - p, base1 = 0, len1 = 0;
-        if (ts_split > 0) {
-          len0 = std::min(pc, ts_split - p);
-          base1 = ts_split;
-          len1 = m - ts_split;
-        }
-        int rows = len0 + len1;
-        int W = rows <= QR_MAX_ROWS_W16 ? 16
-                                        : (rows <= QR_MAX_ROWS_W8 ? 8 : 0);
-        PA_CHECK(W, "bench: rows too large");
-        PA_HIP_CHECK(hipMemsetAsync(cnt, 0, 2 * sizeof(int), s));
-        hipLaunchKernelGGL(k_qr_panel_mw, dim3(nwg), dim3(1024), 0, s, dA,
-                           m, p, base0, len0, base1, len1, k - p, pc, W,
-                           tau + p, T16s, cnt, nwg, nA, cfg.amode, cfg.look,
-                           dbg);
-      }
-    } else {
-      PA_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA, m, tau) ==
+    if (mode == QR_BENCH_FULL) {
+      qr_factor_hand(g, dA.p, m, k, m, dT.p, k, ts_split, cfg);
+    } else if (mode == QR_BENCH_ROCSOLVER) {
+      PA_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA.p, m, tau) ==
                rocblas_status_success);
+    } else {
+      for (int p = 0; p < k; p += 128) {
+        const int pc = std::min(128, k - p);
+        const QrPanelGeom geo = qr_panel_geom(m, p, pc, ts_split);
+        PA_CHECK(geo.W, "bench: rows too large");
+        launch_qr_panel(g, cfg, dA.p, m, p, geo, k - p, pc, tau,
+                        timed ? dbg.p : nullptr);
+      }
     }
-  };
-  run();
-  PA_HIP_CHECK(hipStreamSynchronize(s));
-  double t0 = now_s();
-  for (int i = 0; i < iters; i++) run();
-  PA_HIP_CHECK(hipStreamSynchronize(s));
-  double dt = now_s() - t0;
-  if (dbg) {
+  }, s);
+  if (timed) {
     unsigned long long h[16];
-    PA_HIP_CHECK(hipMemcpy(h, dbg, 16 * 8, hipMemcpyDeviceToHost));
+    dbg.download(h);
     const char* names[] = {"wg0 ack-wait", "wg0 stage", "wg0 factor",
                            "wg0 scale+wb", "wg0 G16+T16", "A poll",
                            "A vbuild", "A apply", "B poll", "B vbuild",
@@ -1512,10 +1501,7 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
     for (int i = 0; i < 11; i++)
       fprintf(stderr, "[qrdbg] %-12s %8.1f us/tile\n", names[i],
               h[i] / 0.1 / (iters + 1));  // 100 MHz ticks
-    PA_HIP_CHECK(hipFree(dbg));
   }
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dT));
   return dt;
 }
 
@@ -1540,10 +1526,7 @@ void test_qr_factor_hip(double* A, size_t a_elems, int m, int k, int lda,
   // their per-thread state on it
   static thread_local hipStream_t s = nullptr;
   if (!s) PA_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  double *dA, *dT;
-  PA_HIP_CHECK(hipMalloc(&dA, a_elems * 8));
-  PA_HIP_CHECK(hipMalloc(&dT, (size_t)k * k * 8));
-  PA_HIP_CHECK(hipMemcpy(dA, A, a_elems * 8, hipMemcpyHostToDevice));
+  DevArray dA(a_elems, A), dT((size_t)k * k);
   std::vector<std::pair<void*, size_t>> defer;
   GpuTaskCtx g{s, 0, nullptr, &defer};
   if (impl == 0) {
@@ -1553,18 +1536,15 @@ void test_qr_factor_hip(double* A, size_t a_elems, int m, int k, int lda,
     if (!apply.empty()) cfg.set_apply(apply);
     if (lookahead >= 0) cfg.look = lookahead;
     cfg.clamp();
-    qr_factor_hand(g, dA, m, k, lda, dT, k, 0, ts_split, cfg);
+    qr_factor_hand(g, dA.p, m, k, lda, dT.p, k, ts_split, cfg);
   } else {
-    qr_factor_rocsolver(g, dA, m, k, lda, dT, k, (size_t)k * k * 8);
+    qr_factor_rocsolver(g, dA.p, m, k, lda, dT.p, k, (size_t)k * k * 8);
   }
   PA_HIP_CHECK(hipStreamSynchronize(s));
-  PA_HIP_CHECK(hipGetLastError());
-  PA_HIP_CHECK(hipMemcpy(A, dA, a_elems * 8, hipMemcpyDeviceToHost));
-  PA_HIP_CHECK(hipMemcpy(T, dT, (size_t)k * k * 8, hipMemcpyDeviceToHost));
+  dA.download(A);
+  dT.download(T);
   // scratch that grew during this call was replaced, not freed
   for (auto& d : defer) PA_HIP_CHECK(hipFree(d.first));
-  PA_HIP_CHECK(hipFree(dA));
-  PA_HIP_CHECK(hipFree(dT));
 }
 
 }  // namespace pa

@@ -149,14 +149,7 @@ void gpu_gemm_nn_sub(Task& t, GpuTaskCtx& g) {
 
 TaskClass make_bc_tc(const char* name, void (*cpu)(Task&),
                      void (*gpu)(Task&, GpuTaskCtx&), int id) {
-  Profiler::inst().register_class(id, name);
-  TaskClass tc;
-  tc.name = name;
-  tc.kind = TaskKind::GPU;
-  tc.cpu_hook = cpu;
-  tc.gpu_hook = gpu;
-  tc.id = id;
-  return tc;
+  return make_tc(name, TaskKind::GPU, cpu, gpu, id);
 }
 
 TaskClass& tc_gemm_tn_acc() {

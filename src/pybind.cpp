@@ -17,6 +17,7 @@
 #include "dtd.hpp"
 #include "gpu_graph.hpp"
 #include "kernels.hpp"
+#include "kernels_bench.hpp"
 #include "kernels_hip.hpp"
 #include "pins.hpp"
 #include "profiling.hpp"
@@ -25,12 +26,6 @@
 namespace pa {
 std::string rccl_get_unique_id();
 void rccl_set_unique_id(const std::string&);
-double bench_dgemm_rocblas(int, int, int, int);
-double bench_tn_rocblas(int, int, int, int, int);
-double bench_gemm_bf16(int, int, int, int);
-double bench_qr_factor(int, int, int, int, int);
-void test_gemm_bf16_hip(int, int, int, const uint16_t*, const uint16_t*,
-                        float*);
 }  // namespace pa
 
 namespace py = pybind11;
@@ -681,8 +676,9 @@ PYBIND11_MODULE(_core, m) {
     auto it = impls.find(impl);
     if (it == impls.end())
       throw std::invalid_argument("qr_factor_hip: impl hand|rocsolver|cpu");
-    if (wgs != 0 && (wgs < 2 || wgs > 48))
-      throw std::invalid_argument("qr_factor_hip: wgs is 0 or in [2, 48]");
+    if (wgs != 0 && (wgs < 2 || wgs > QR_PANEL_MAX_WGS))
+      throw std::invalid_argument("qr_factor_hip: wgs is 0 or in [2, " +
+                                  std::to_string(QR_PANEL_MAX_WGS) + "]");
     if (poolA < 0 || lookahead < -1 || lookahead > 1 ||
         (!apply.empty() && apply != "kernel" && apply != "valu" &&
          apply != "gemm"))
