@@ -26,6 +26,22 @@ struct TileArgs {
   uint32_t seed = 0;
 };
 
+// Arguments of tc_gemm_nn: C = alpha op(A) B + beta C.
+struct GemmNNArgs {
+  int m, n, k, lda, ldb, ldc;
+  double alpha, beta;
+  int transA = 0;  // 1: C = alpha*A^T*B + beta*C
+};
+
+// Arguments of tc_trsm_solve: a triangular solve from the left with the
+// factor in a diagonal tile.
+struct TrsmSolveArgs {
+  int m, n, lda, ldb;
+  int trans;  // 0: solve T Z = B; 1: solve T^T Z = B
+  int upper = 0;  // triangle of the diagonal tile holding the factor
+  int unit = 0;   // unit diagonal (LU's L)
+};
+
 // A task class with a CPU and a GPU incarnation, registered with the
 // profiler under `id` (kernels_blas.cpp). Every kernels_*.cpp builds its
 // classes through this.
@@ -39,6 +55,9 @@ TaskClass& tc_trsm();
 TaskClass& tc_syrk();
 TaskClass& tc_gemm();
 TaskClass& tc_gemm_nn();
+TaskClass& tc_trsm_solve();
+// PARSEC_MCA_chore_gemm_nn=hip: C -= A B tasks take the hand NN kernel.
+bool gemm_nn_hip();
 
 TaskClass& tc_trtri();
 TaskClass& tc_trsm_inv();
@@ -51,6 +70,7 @@ TaskClass& tc_tsmqr();
 void insert_spd_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_full_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_potrf(Dtd& tp, TiledMatrix& A);
+// Householder tile QR, M >= N: R in the upper tiles, reflectors not kept.
 void insert_geqrf(Dtd& tp, TiledMatrix& A);
 // QR by block Gram-Schmidt with CholeskyQR2 panels (matrix-core rates;
 // cond(A) <~ 1e7): A becomes the explicit orthonormal Q, R the upper
@@ -89,6 +109,11 @@ void insert_gesv_nopiv(Dtd& tp, TiledMatrix& A, TiledMatrix& B);
 // Least squares via BCGS QR (dgels analog): X = R^-1 Q^T B.
 void insert_gels_bcgs(Dtd& tp, TiledMatrix& A, TiledMatrix& R,
                       TiledMatrix& B, TiledMatrix& X);
+// Householder least squares / solve (dgels analog, M >= N, full column
+// rank; a square A makes it the general solver): A's upper tiles get R as
+// after insert_geqrf, rows [0, N) of B get X, rows [N, M) the residual part
+// of Q^T B (kernels_qr.cpp).
+void insert_gels(Dtd& tp, TiledMatrix& A, TiledMatrix& B);
 void insert_reduce_sum(Dtd& tp, TiledMatrix& A, TiledMatrix& R);
 // log-depth binary-tree variant (BT_reduction.jdf analog).
 void insert_reduce_sum_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& R);

@@ -51,6 +51,7 @@ double time_launches(int iters, F run, hipStream_t stream = nullptr) {
 // Timed library loops for the A/B against the hand kernels; seconds for
 // `iters` calls (kernels_blas.cpp).
 double bench_dgemm_rocblas(int m, int n, int k, int iters);
+double bench_dgemm_nn_rocblas(int m, int n, int k, int iters);
 double bench_tn_rocblas(int kind, int m, int n, int k, int iters);
 
 // bf16 GEMM: TFLOP/s of the kernel, and its host-memory test entry

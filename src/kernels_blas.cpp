@@ -328,23 +328,34 @@ static void gpu_gemm(Task& t, GpuTaskCtx& g) {
 }
 
 // Timed rocBLAS dgemm NT loop for kernel-level A/B against the hand kernel.
-double bench_dgemm_rocblas(int m, int n, int k, int iters) {
+// C -= A B^T (B stored n x k) or, with nn, C -= A B (B stored k x n).
+static double bench_dgemm_lib(int m, int n, int k, int iters, bool nn) {
+  const int brows = nn ? k : n, bcols = nn ? n : k;
   DevArray dA((size_t)m * k), dB((size_t)n * k), dC((size_t)m * n);
   hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dA.p, m, k, m,
                      0, 0, 0, 11u);
-  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dB.p, n, k, n,
-                     7, 3, 0, 12u);
+  hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dB.p, brows,
+                     bcols, brows, 7, 3, 0, 12u);
   hipLaunchKernelGGL(k_spd_fill, dim3(2048), dim3(256), 0, 0, dC.p, m, n, m,
                      1, 9, 0, 13u);
   rocblas_handle h;
   PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
   const double mone = -1.0, one = 1.0;
   double dt = time_launches(iters, [&] {
-    rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_transpose, m,
-                  n, k, &mone, dA.p, m, dB.p, n, &one, dC.p, m);
+    rocblas_dgemm(h, rocblas_operation_none,
+                  nn ? rocblas_operation_none : rocblas_operation_transpose, m,
+                  n, k, &mone, dA.p, m, dB.p, brows, &one, dC.p, m);
   });
   rocblas_destroy_handle(h);
   return dt;
+}
+
+double bench_dgemm_rocblas(int m, int n, int k, int iters) {
+  return bench_dgemm_lib(m, n, k, iters, /*nn=*/false);
+}
+
+double bench_dgemm_nn_rocblas(int m, int n, int k, int iters) {
+  return bench_dgemm_lib(m, n, k, iters, /*nn=*/true);
 }
 
 // ------------------------------------------------------------------ classes
@@ -969,12 +980,6 @@ void insert_potrf(Dtd& tp, TiledMatrix& A) {
 // (beta = 0, OUTPUT flow), later k accumulate — which makes the whole DAG
 // IDEMPOTENT: replaying it (e.g. from a captured hipGraph, gpu_graph.hpp)
 // reproduces the same C from the same A/B.
-struct GemmNNArgs {
-  int m, n, k, lda, ldb, ldc;
-  double alpha, beta;
-  int transA = 0;  // 1: C = alpha*A^T*B + beta*C
-};
-
 static void cpu_gemm_nn(Task& t) {
   const GemmNNArgs& a = t.arg<GemmNNArgs>();
   const double* A = (const double*)t.flows[0].data->pull_to_host();
@@ -1009,8 +1014,22 @@ __global__ void k_gemm_nn_thin(int m, int n, int k, double alpha,
   C[(size_t)j * ldc + i] = c0 + alpha * s;
 }
 
+bool gemm_nn_hip() {
+  static const bool v = param_str("chore_gemm_nn", "rocblas") == "hip";
+  return v;
+}
+
 static void gpu_gemm_nn(Task& t, GpuTaskCtx& g) {
   const GemmNNArgs& a = t.arg<GemmNNArgs>();
+  // chore_gemm_nn=hip: the update of a solve sweep, C -= A B, on more than
+  // the thin kernel's columns
+  if (gemm_nn_hip() && !a.transA && a.alpha == -1.0 && a.beta == 1.0 &&
+      a.n > 4) {
+    launch_dgemm_nn(a.m, a.n, a.k, (const double*)t.dev_ptr[0], a.lda,
+                    (const double*)t.dev_ptr[1], a.ldb, (double*)t.dev_ptr[2],
+                    a.ldc, g.stream);
+    return;
+  }
   if (a.n <= 4 && !a.transA) {
     hipLaunchKernelGGL(k_gemm_nn_thin, dim3((a.m + 63) / 64, a.n), dim3(64),
                        0, g.stream, a.m, a.n, a.k, a.alpha,
@@ -1081,13 +1100,6 @@ void insert_advise_prefetch(Dtd& tp, Data* d) {
 // L^T X = Y. Diagonal solves are rocblas_dtrsm (left, lower, N/T);
 // off-diagonal updates reuse the gemm_nn chore (alpha=-1, beta=1, with
 // transA for the backward sweep).
-struct TrsmSolveArgs {
-  int m, n, lda, ldb;
-  int trans;  // 0: solve T Z = B; 1: solve T^T Z = B
-  int upper = 0;  // triangle of the diagonal tile holding the factor
-  int unit = 0;   // unit diagonal (LU's L)
-};
-
 static void cpu_trsm_solve(Task& t) {
   const TrsmSolveArgs& a = t.arg<TrsmSolveArgs>();
   const double* L = (const double*)t.flows[0].data->pull_to_host();

@@ -36,6 +36,9 @@
 //  - k_dgemm_tn<KIND>, the bounds-checked kernel for C (+)= A^T B with
 //    triangular kinds: the LAUUM phase of the SPD inverse
 //    (chore_lauum=hip|rocblas, chore_gemm_tn=hip|rocblas).
+//  - k_dgemm_nn, the bounds-checked kernel for C -= A B: the update of the
+//    triangular solve sweeps and LU's trailing update
+//    (chore_gemm_nn=hip|rocblas).
 //  - k_potf2_mfma, the in-LDS Cholesky of one <=128 diagonal block.
 #include "kernels_hip.hpp"
 
@@ -345,6 +348,61 @@ __global__ void k_dgemm_tn(int m, int n, int k, const double* __restrict__ A,
           /*checked=*/true, /*store=*/STORE);
 }
 
+// ------------------------------------------------------------------ nn
+// C[m x n] -= A[m x k] B[k x n]: A is contiguous along M and staged as v2
+// stages its A, B is contiguous along K and staged as the TN kernel stages
+// its B (read along K, written transposed), both into the same [k][129] LDS
+// image, zero-filled outside m, n and k.
+__launch_bounds__(512)
+__global__ void k_dgemm_nn(int m, int n, int k, const double* __restrict__ A,
+                           int lda, const double* __restrict__ B, int ldb,
+                           double* __restrict__ C, int ldc, int nbx) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int LDT = 129;
+  double* As = (double*)smem;                  // [2][BKD][LDT]
+  double* Bs = As + 2 * BKD * LDT;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  int bx, by;
+  block_decode(false, nbx, bx, by);
+  const int bm0 = bx * BM, bn0 = by * BN;
+  const int ksub = lane >> 4, r16 = lane & 15;
+
+  f64x4 acc[2][4] = {};
+
+  auto stage = [&](int buf, int k0) {
+    double* as = As + buf * BKD * LDT;
+    double* bs = Bs + buf * BKD * LDT;
+#pragma unroll
+    for (int x = 0; x < BM * BKD; x += 512) {
+      int xi = x + tid;
+      int i = xi & (BM - 1), kk = xi >> 7;
+      int gi = bm0 + i, gk = k0 + kk;
+      as[kk * LDT + i] = (gi < m && gk < k) ? A[(size_t)gk * lda + gi] : 0.0;
+    }
+#pragma unroll
+    for (int x = 0; x < BN * BKD; x += 512) {
+      int xi = x + tid;
+      int kk = xi & (BKD - 1), j = xi / BKD;
+      int gj = bn0 + j, gk = k0 + kk;
+      bs[kk * LDT + j] = (gj < n && gk < k) ? B[(size_t)gj * ldb + gk] : 0.0;
+    }
+  };
+
+  stage(0, 0);
+  __syncthreads();
+  const int ntiles = (k + BKD - 1) / BKD;
+  for (int t = 0; t < ntiles; t++) {
+    if (t + 1 < ntiles) stage((t + 1) & 1, (t + 1) * BKD);
+    mfma_ktile(acc, As + ((t & 1) * BKD + ksub) * LDT + wr * 32 + r16,
+               Bs + ((t & 1) * BKD + ksub) * LDT + wc * 64 + r16, LDT);
+    __syncthreads();
+  }
+  write_c(acc, C, ldc, bm0 + wr * 32 + ksub, bn0 + wc * 64 + r16, m, n,
+          /*checked=*/true, /*store=*/false);
+}
+
 // ------------------------------------------------------------- launchers
 // Every kernel here asks for more dynamic LDS than a launch gets by
 // default: raise that kernel's limit once, then launch.
@@ -416,6 +474,17 @@ void launch_dgemm_tn(int m, int n, int k, const double* A, int lda,
   const int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
   launch_lds<k_dgemm_tn<TN_GEMM>>(nbx * nby, 512, LDS_V2, stream, m, n, k, A,
                                   lda, B, ldb, C, ldc, nbx);
+}
+
+void launch_dgemm_nn(int m, int n, int k, const double* A, int lda,
+                     const double* B, int ldb, double* C, int ldc,
+                     hipStream_t stream) {
+  PA_CHECK(m > 0 && n > 0 && k > 0 && lda >= m && ldb >= k && ldc >= m,
+           "dgemm_nn: bad shape %d x %d x %d, ld %d %d %d", m, n, k, lda, ldb,
+           ldc);
+  const int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
+  launch_lds<k_dgemm_nn>(nbx * nby, 512, LDS_V2, stream, m, n, k, A, lda, B,
+                         ldb, C, ldc, nbx);
 }
 
 void launch_dsyrk_lt(int n, int k, const double* A, int lda, double* C,
@@ -591,6 +660,14 @@ void test_dgemm_tn_hip(int m, int n, int k, const double* A, int lda,
   dC.download(C);
 }
 
+void test_dgemm_nn_hip(int m, int n, int k, const double* A, int lda,
+                       const double* B, int ldb, double* C, int ldc) {
+  DevArray dA((size_t)lda * k, A), dB((size_t)ldb * n, B),
+      dC((size_t)ldc * n, C);
+  launch_dgemm_nn(m, n, k, dA.p, lda, dB.p, ldb, dC.p, ldc, 0);
+  dC.download(C);
+}
+
 void test_dsyrk_lt_hip(int n, int k, const double* A, int lda, double* C,
                        int ldc) {
   DevArray dA((size_t)lda * n, A), dC((size_t)ldc * n, C);
@@ -650,6 +727,17 @@ double bench_dgemm_tn_hip(int kind, int m, int n, int k, int iters) {
       case TN_TRMM: launch_dtrmm_llt(m, n, dA.p, m, dB.p, m, dC.p, m, 0); break;
       default: launch_dlauum_l(n, dA.p, n, dC.p, n, 0);
     }
+  });
+}
+
+// The rocBLAS comparison is bench_dgemm_nn_rocblas in kernels_blas.cpp.
+double bench_dgemm_nn_hip(int m, int n, int k, int iters) {
+  DevArray dA((size_t)m * k), dB((size_t)k * n), dC((size_t)m * n);
+  bench_fill(dA, 11);
+  bench_fill(dB, 12);
+  bench_fill(dC, 13);
+  return time_launches(iters, [&] {
+    launch_dgemm_nn(m, n, k, dA.p, m, dB.p, k, dC.p, m, 0);
   });
 }
 

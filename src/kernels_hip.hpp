@@ -39,6 +39,11 @@ void launch_dtrmm_llt(int m, int n, const double* W, int ldw, const double* B,
 // and its other blocks are left alone
 void launch_dlauum_l(int n, const double* W, int ldw, double* X, int ldx,
                      hipStream_t stream);
+// C[m x n] -= A[m x k] * B[k x n], bounds-checked: any shape and leading
+// dimension
+void launch_dgemm_nn(int m, int n, int k, const double* A, int lda,
+                     const double* B, int ldb, double* C, int ldc,
+                     hipStream_t stream);
 // In-place lower Cholesky of an n x n block, n <= 128; the strict upper
 // triangle is neither read nor written.
 void launch_potf2(double* A, int n, int ld, hipStream_t stream);
@@ -56,6 +61,8 @@ void test_dtrmm_rlt_hip(int m, int n, const double* B, int ldb,
                         const double* W, int ldw, double* X, int ldx);
 void test_dgemm_tn_hip(int m, int n, int k, const double* A, int lda,
                        const double* B, int ldb, double* C, int ldc);
+void test_dgemm_nn_hip(int m, int n, int k, const double* A, int lda,
+                       const double* B, int ldb, double* C, int ldc);
 void test_dsyrk_lt_hip(int n, int k, const double* A, int lda, double* C,
                        int ldc);
 void test_dtrmm_llt_hip(int m, int n, const double* W, int ldw,
@@ -67,6 +74,7 @@ void test_potf2_hip(double* A, int n);
 double bench_dgemm_hip(int m, int n, int k, int iters);
 // kind 0 gemm (m, n, k), 1 syrk (n, k), 2 trmm (m, n), 3 lauum (n)
 double bench_dgemm_tn_hip(int kind, int m, int n, int k, int iters);
+double bench_dgemm_nn_hip(int m, int n, int k, int iters);
 double bench_dtrmm_hip(int m, int n, int iters);
 
 }  // namespace pa

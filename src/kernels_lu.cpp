@@ -6,7 +6,8 @@
 // left, unit-lower), TRSM_U(m,k) column panel (U^-1 from the right),
 // GEMM_NN(m,n) trailing update A(m,n) -= A(m,k) A(k,n).
 // GPU chores: rocSOLVER getrf_npvt (on a blocking worker, QR-panel
-// pattern) + rocBLAS trsm/gemm. CPU chores: reference loops for the
+// pattern) + rocBLAS trsm/gemm; chore_gemm_nn=hip puts the trailing update
+// on the hand NN kernel. CPU chores: reference loops for the
 // no-GPU test path.
 #include <cstring>
 
@@ -17,6 +18,7 @@
 #include "device_gpu.hpp"
 #include "gpu_blas.hpp"
 #include "kernels.hpp"
+#include "kernels_hip.hpp"
 #include "profiling.hpp"
 
 namespace pa {
@@ -208,6 +210,12 @@ void gpu_trsm_u(Task& t, GpuTaskCtx& g) {
 
 void gpu_gemm_nn(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
+  if (gemm_nn_hip()) {
+    launch_dgemm_nn(a.m, a.n, a.k, (const double*)t.dev_ptr[0], a.ld,
+                    (const double*)t.dev_ptr[1], a.ld, (double*)t.dev_ptr[2],
+                    a.ld, g.stream);
+    return;
+  }
   const double mone = -1.0, one = 1.0;
   PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
                          rocblas_operation_none, a.m, a.n, a.k, &mone,

@@ -1341,14 +1341,36 @@ TaskClass& tc_tsmqr() {
 }
 
 // ------------------------------------------------------------ DAG builder
+// The trailing columns of one QR sweep: A's own column tiles and, when a
+// right-hand side rides along (insert_gels), B's column tiles after them.
+// Trailing column n >= A.nt() is B's column tile n - A.nt(); it keeps that
+// index in the priority formulas, so every A column goes first.
+namespace {
+struct QrTrail {
+  TiledMatrix& A;
+  TiledMatrix* B;
+  int end() const { return A.nt() + (B ? B->nt() : 0); }
+  Data* tile(int m, int n) const {
+    return n < A.nt() ? A.tile(m, n) : B->tile(m, n - A.nt());
+  }
+  int rank_of(int m, int n) const {
+    return n < A.nt() ? A.rank_of(m, n) : B->rank_of(m, n - A.nt());
+  }
+  int cols(int n) const {
+    return n < A.nt() ? A.nb() : B->tile_cols(n - A.nt());
+  }
+};
+}  // namespace
+
 // Binary TS-reduction tree per panel column (the reference ecosystem's
 // HQR trees): every row tile is GEQRT'd independently (level 0), then
 // pairs combine through TSQRT/TSMQR with stride-doubling — panel depth
 // O(log M) instead of O(M). More total flops than the flat chain (the
 // per-row UNMQR applies), but the host-synced panel kernels run
 // CONCURRENTLY on blocking workers, which is what bounds QR here.
-static void insert_geqrf_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& WT,
+static void insert_geqrf_tree(Dtd& tp, const QrTrail& tr, TiledMatrix& WT,
                               TiledMatrix& T1, TiledMatrix& V2) {
+  TiledMatrix& A = tr.A;
   const int T = A.mt();
   const int nb = A.nb(), ld = A.mb();
   constexpr int PANEL = 1 << 20;
@@ -1356,19 +1378,21 @@ static void insert_geqrf_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& WT,
   pa_args.m = nb;
   pa_args.n = nb;
   pa_args.ld = ld;
-  for (int k = 0; k < T; k++) {
+  for (int k = 0; k < A.nt(); k++) {
     // level 0: factor every row tile of the column, apply across its row
     for (int m = k; m < T; m++) {
       Dtd::FlowSpec f[] = {{A.tile(m, k), ACCESS_INOUT},
                            {WT.tile(m, k), ACCESS_OUT}};
       tp.insert(&tc_geqrt(), &pa_args, sizeof(pa_args), f, 2, PANEL + 1,
                 A.rank_of(m, k));
-      for (int n = k + 1; n < T; n++) {
+      for (int n = k + 1; n < tr.end(); n++) {
+        TileArgs ua = pa_args;
+        ua.n = tr.cols(n);
         Dtd::FlowSpec fu[] = {{A.tile(m, k), ACCESS_IN},
                               {WT.tile(m, k), ACCESS_IN},
-                              {A.tile(m, n), ACCESS_INOUT}};
-        tp.insert(&tc_unmqr(), &pa_args, sizeof(pa_args), fu, 3,
-                  (1 << 18) - (n - k), A.rank_of(m, n));
+                              {tr.tile(m, n), ACCESS_INOUT}};
+        tp.insert(&tc_unmqr(), &ua, sizeof(ua), fu, 3, (1 << 18) - (n - k),
+                  tr.rank_of(m, n));
       }
     }
     // reduction tree: combine (a, a+step) pairs, doubling the stride
@@ -1385,24 +1409,29 @@ static void insert_geqrf_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& WT,
           tp.insert(&tc_tsqrt(), &ta, sizeof(ta), f, 4, PANEL,
                     A.rank_of(b, k));
         }
-        for (int n = k + 1; n < T; n++) {
+        for (int n = k + 1; n < tr.end(); n++) {
+          TileArgs ua = pa_args;
+          ua.n = tr.cols(n);
           Dtd::FlowSpec f[] = {{V2.tile(b, k), ACCESS_IN},
                                {T1.tile(b, k), ACCESS_IN},
-                               {A.tile(a, n), ACCESS_INOUT},
-                               {A.tile(b, n), ACCESS_INOUT}};
-          tp.insert(&tc_tsmqr(), &pa_args, sizeof(pa_args), f, 4,
-                    -(n - k) * 4, A.rank_of(b, n));
+                               {tr.tile(a, n), ACCESS_INOUT},
+                               {tr.tile(b, n), ACCESS_INOUT}};
+          tp.insert(&tc_tsmqr(), &ua, sizeof(ua), f, 4, -(n - k) * 4,
+                    tr.rank_of(b, n));
         }
       }
     }
   }
 }
 
-void insert_geqrf(Dtd& tp, TiledMatrix& A) {
+// The QR sweep of A (M >= N, whole square tiles) over k < A.nt(), m < A.mt().
+// With B, its column tiles are trailing columns too and end up holding
+// Q^T B. For square A without B this inserts what insert_geqrf always did:
+// the same tasks in the same order with the same priorities and ranks.
+static void insert_qr_sweep(Dtd& tp, TiledMatrix& A, TiledMatrix* B) {
+  const QrTrail tr{A, B};
   const int T = A.mt();
   const int nb = A.nb(), ld = A.mb();
-  PA_CHECK(A.m() % nb == 0 && A.mb() == A.nb(),
-           "insert_geqrf: N must be a multiple of the (square) tile size");
   constexpr int PANEL = 1 << 20;
   auto* ctx = A.ctx();
   auto WT = std::make_shared<TiledMatrix>(ctx, A.m(), A.n(), nb, nb,
@@ -1415,10 +1444,10 @@ void insert_geqrf(Dtd& tp, TiledMatrix& A) {
   tp.own(T1);
   tp.own(V2);
   if (param_str("qr_tree", "flat") == "binary") {
-    insert_geqrf_tree(tp, A, *WT, *T1, *V2);
+    insert_geqrf_tree(tp, tr, *WT, *T1, *V2);
     return;
   }
-  for (int k = 0; k < T; k++) {
+  for (int k = 0; k < A.nt(); k++) {
     TileArgs pa_args;
     pa_args.m = nb;
     pa_args.n = nb;
@@ -1429,12 +1458,14 @@ void insert_geqrf(Dtd& tp, TiledMatrix& A) {
       tp.insert(&tc_geqrt(), &pa_args, sizeof(pa_args), f, 2, PANEL + 1,
                 A.rank_of(k, k));
     }
-    for (int n = k + 1; n < T; n++) {
+    for (int n = k + 1; n < tr.end(); n++) {
+      TileArgs ua = pa_args;
+      ua.n = tr.cols(n);
       Dtd::FlowSpec f[] = {{A.tile(k, k), ACCESS_IN},
                            {WT->tile(k, k), ACCESS_IN},
-                           {A.tile(k, n), ACCESS_INOUT}};
-      tp.insert(&tc_unmqr(), &pa_args, sizeof(pa_args), f, 3,
-                (1 << 18) - (n - k), A.rank_of(k, n));
+                           {tr.tile(k, n), ACCESS_INOUT}};
+      tp.insert(&tc_unmqr(), &ua, sizeof(ua), f, 3, (1 << 18) - (n - k),
+                tr.rank_of(k, n));
     }
     for (int m = k + 1; m < T; m++) {
       {
@@ -1445,16 +1476,68 @@ void insert_geqrf(Dtd& tp, TiledMatrix& A) {
         tp.insert(&tc_tsqrt(), &pa_args, sizeof(pa_args), f, 4, PANEL,
                   A.rank_of(m, k));
       }
-      for (int n = k + 1; n < T; n++) {
+      for (int n = k + 1; n < tr.end(); n++) {
+        TileArgs ua = pa_args;
+        ua.n = tr.cols(n);
         Dtd::FlowSpec f[] = {{V2->tile(m, k), ACCESS_IN},
                              {T1->tile(m, k), ACCESS_IN},
-                             {A.tile(k, n), ACCESS_INOUT},
-                             {A.tile(m, n), ACCESS_INOUT}};
-        tp.insert(&tc_tsmqr(), &pa_args, sizeof(pa_args), f, 4,
-                  -(n - k) * 4, A.rank_of(m, n));
+                             {tr.tile(k, n), ACCESS_INOUT},
+                             {tr.tile(m, n), ACCESS_INOUT}};
+        tp.insert(&tc_tsmqr(), &ua, sizeof(ua), f, 4, -(n - k) * 4,
+                  tr.rank_of(m, n));
       }
     }
   }
+}
+
+// Tall A (M >= N) is accepted: the sweep runs over A.nt() panel columns and
+// A.mt() row tiles, and R ends up in the upper tiles of the first A.nt()
+// tile rows.
+void insert_geqrf(Dtd& tp, TiledMatrix& A) {
+  PA_CHECK(A.m() % A.nb() == 0 && A.n() % A.nb() == 0 && A.mb() == A.nb() &&
+               A.m() >= A.n(),
+           "insert_geqrf: M >= N, both multiples of the (square) tile size");
+  insert_qr_sweep(tp, A, nullptr);
+}
+
+// Householder least squares / solve (LAPACK dgels, M >= N, full column
+// rank) without keeping Q: B's column tiles ride through the QR sweep of A as
+// extra trailing columns and receive Q^T B, then one backward sweep with R
+// leaves X in B's first N rows. Rows [N, M) of B keep the part of Q^T B
+// orthogonal to range(A): its column norms are the residual norms. The
+// diagonal solves are true triangular solves, as this entry point is the
+// one for ill-conditioned input.
+void insert_gels(Dtd& tp, TiledMatrix& A, TiledMatrix& B) {
+  PA_CHECK(A.mb() == A.nb(), "insert_gels: A needs square tiles, got %d x %d",
+           A.mb(), A.nb());
+  PA_CHECK(A.m() % A.nb() == 0 && A.n() % A.nb() == 0,
+           "insert_gels: M and N must be multiples of the tile size %d",
+           A.nb());
+  PA_CHECK(A.m() >= A.n(), "insert_gels: M >= N (overdetermined or square)");
+  PA_CHECK(B.mb() == A.mb() && B.mt() == A.mt(),
+           "insert_gels: B must have A's row tiling (mb %d, mt %d)", A.mb(),
+           A.mt());
+  PA_CHECK(A.elem_size() == 8 && B.elem_size() == 8 && A.ctx() == B.ctx(),
+           "insert_gels: fp64 matrices of one context");
+  insert_qr_sweep(tp, A, &B);
+  // backward: R X = (Q^T B)[0:N], R upper non-unit
+  const int nb = A.nb(), ld = A.mb();
+  for (int j = 0; j < B.nt(); j++)
+    for (int k = A.nt() - 1; k >= 0; k--) {
+      TrsmSolveArgs a{nb, B.tile_cols(j), ld, ld, 0};
+      a.upper = 1;
+      Dtd::FlowSpec f[] = {{A.tile(k, k), ACCESS_IN},
+                           {B.tile(k, j), ACCESS_INOUT}};
+      tp.insert(&tc_trsm_solve(), &a, sizeof(a), f, 2, (1 << 20),
+                B.rank_of(k, j));
+      for (int i = k - 1; i >= 0; i--) {
+        GemmNNArgs a2{nb, B.tile_cols(j), nb, ld, ld, ld, -1.0, 1.0};
+        Dtd::FlowSpec f2[] = {{A.tile(i, k), ACCESS_IN},
+                              {B.tile(k, j), ACCESS_IN},
+                              {B.tile(i, j), ACCESS_INOUT}};
+        tp.insert(&tc_gemm_nn(), &a2, sizeof(a2), f2, 3, 0, B.rank_of(i, j));
+      }
+    }
 }
 
 // Standalone micro-benchmark of the TS/tile panel factorization path, by

@@ -463,6 +463,8 @@ PYBIND11_MODULE(_core, m) {
   m.def("insert_gels_bcgs", &insert_gels_bcgs, py::arg("tp"), py::arg("A"),
         py::arg("R"), py::arg("B"), py::arg("X"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("insert_gels", &insert_gels, py::arg("tp"), py::arg("A"),
+        py::arg("B"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_advise_prefetch", &insert_advise_prefetch, py::arg("tp"),
         py::arg("tile"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_gemm_fp64", &insert_gemm_fp64, py::arg("tp"), py::arg("A"),
@@ -604,6 +606,37 @@ PYBIND11_MODULE(_core, m) {
                           C.mutable_data(), ldc);
   }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
      py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+  m.def("dgemm_nn_hip", [](py::array_t<double> A, py::array_t<double> B,
+                           py::array_t<double> C, int m, int n, int k, int lda,
+                           int ldb, int ldc) {
+    // C[m x n] -= A[m x k] * B[k x n]; column-major buffers flattened 1-D
+    // with k / n / n columns of lda / ldb / ldc doubles each (0: the rows)
+    if (lda == 0) lda = m;
+    if (ldb == 0) ldb = k;
+    if (ldc == 0) ldc = m;
+    if (m <= 0 || n <= 0 || k <= 0 || lda < m || ldb < k || ldc < m ||
+        A.size() < (py::ssize_t)lda * k || B.size() < (py::ssize_t)ldb * n ||
+        C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("dgemm_nn_hip: buffer smaller than ld*cols");
+    pa::test_dgemm_nn_hip(m, n, k, A.data(), lda, B.data(), ldb,
+                          C.mutable_data(), ldc);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+  // which chore this process's C -= A B tile tasks take: "hip" | "rocblas"
+  m.def("chore_gemm_nn", [] {
+    return std::string(pa::gemm_nn_hip() ? "hip" : "rocblas");
+  });
+  // TFLOP/s of C -= A B at m x n x k; impl "hip" is the hand kernel,
+  // "rocblas" the library dgemm
+  m.def("bench_dgemm_nn_hip", [](int m, int n, int k, int iters,
+                                 std::string impl) {
+    if ((impl != "hip" && impl != "rocblas") || iters <= 0)
+      throw std::invalid_argument("bench_dgemm_nn_hip: impl hip|rocblas");
+    double dt = impl == "hip" ? pa::bench_dgemm_nn_hip(m, n, k, iters)
+                              : pa::bench_dgemm_nn_rocblas(m, n, k, iters);
+    return 2.0 * m * n * k * iters / dt / 1e12;
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+     py::arg("impl") = "hip", py::call_guard<py::gil_scoped_release>());
   m.def("dsyrk_lt_hip", [](py::array_t<double> A, py::array_t<double> C, int n,
                            int k, int lda, int ldc) {
     // C[n x n](lower blocks) += A[k x n]^T * A
