@@ -519,7 +519,7 @@ class TcpComm : public CommEngine {
     }
   }
 
-  Context* ctx_;
+  [[maybe_unused]] Context* ctx_;
   int rank_, world_;
   std::vector<Peer> peers_;
   int wake_pipe_[2] = {-1, -1};

@@ -70,17 +70,18 @@ GpuEngine::~GpuEngine() {
   if (manager_.joinable()) manager_.join();
   PA_HIP_CHECK(hipSetDevice(device_));
   for (auto& dr : draining_) {
-    hipEventSynchronize(dr.ev);  // writebacks must land before teardown
-    hipEventDestroy(dr.ev);
+    // teardown: a failing call has nobody left to report to
+    (void)hipEventSynchronize(dr.ev);  // writebacks must land before teardown
+    (void)hipEventDestroy(dr.ev);
   }
-  for (auto& e : event_pool_) hipEventDestroy(e);
-  for (auto& e : tev_pool_) hipEventDestroy(e);
-  if (ref_ev_) hipEventDestroy(ref_ev_);
-  for (auto s : exec_streams_) hipStreamDestroy(s);
-  hipStreamDestroy(h2d_stream_);
-  hipStreamDestroy(d2h_stream_);
-  hipStreamDestroy(comm_stream_);
-  if (slab_) hipFree(slab_);
+  for (auto& e : event_pool_) (void)hipEventDestroy(e);
+  for (auto& e : tev_pool_) (void)hipEventDestroy(e);
+  if (ref_ev_) (void)hipEventDestroy(ref_ev_);
+  for (auto s : exec_streams_) (void)hipStreamDestroy(s);
+  (void)hipStreamDestroy(h2d_stream_);
+  (void)hipStreamDestroy(d2h_stream_);
+  (void)hipStreamDestroy(comm_stream_);
+  if (slab_) (void)hipFree(slab_);
 }
 
 // Resolve the GPU's NUMA node and its CPU list via sysfs
@@ -513,8 +514,8 @@ bool GpuEngine::retire_pass() {
       if (f.start_ev) {
         // device-side span on this exec stream: its own trace lane
         float ms0 = 0, ms1 = 0;
-        hipEventElapsedTime(&ms0, ref_ev_, f.start_ev);
-        hipEventElapsedTime(&ms1, ref_ev_, f.event);
+        (void)hipEventElapsedTime(&ms0, ref_ev_, f.start_ev);
+        (void)hipEventElapsedTime(&ms1, ref_ev_, f.event);
         if (pr.enabled())
           pr.record_tid(Ev::GPU_SPAN, (uint16_t)t->tc->id, t->seq,
                         ref_ns_ + (uint64_t)((double)ms0 * 1e6),
@@ -627,11 +628,11 @@ void Data::drop_buffers() {
   dev_ptr = nullptr;
   dev_valid = false;
   if (d2h_pending) {  // writeback still in flight targets host_ptr
-    hipEventSynchronize((hipEvent_t)d2h_event);
+    (void)hipEventSynchronize((hipEvent_t)d2h_event);
     d2h_pending = false;
   }
-  if (h2d_event) hipEventDestroy((hipEvent_t)h2d_event);
-  if (d2h_event) hipEventDestroy((hipEvent_t)d2h_event);
+  if (h2d_event) (void)hipEventDestroy((hipEvent_t)h2d_event);
+  if (d2h_event) (void)hipEventDestroy((hipEvent_t)d2h_event);
   h2d_event = d2h_event = nullptr;
   h2d_pending = false;
   if (host_ptr) free(host_ptr);

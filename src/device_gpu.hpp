@@ -119,7 +119,7 @@ class GpuEngine {
   hipEvent_t event_get();
   void event_put(hipEvent_t e);
 
-  Context* ctx_;
+  [[maybe_unused]] Context* ctx_;
   int device_;
   int numa_node_ = -1;
   std::vector<int> numa_cpus_;

@@ -15,7 +15,17 @@
 
 #include <rocblas/rocblas.h>
 
+#include "data.hpp"
 #include "device_gpu.hpp"
+
+// Evaluate a rocBLAS / rocSOLVER call; any status but success is fatal.
+#define PA_BLAS_CHECK(expr)                                                  \
+  do {                                                                       \
+    rocblas_status _s = (expr);                                              \
+    if (_s != rocblas_status_success)                                        \
+      ::pa::fatal("rocBLAS status %d at %s:%d: %s", (int)_s, __FILE__,       \
+                  __LINE__, #expr);                                          \
+  } while (0)
 
 namespace pa {
 
@@ -23,7 +33,7 @@ inline rocblas_handle blas_handle(GpuTaskCtx& g) {
   static thread_local std::map<void*, rocblas_handle> handles;
   rocblas_handle& h = handles[(void*)g.stream];
   if (!h) {
-    PA_CHECK(rocblas_create_handle(&h) == rocblas_status_success);
+    PA_BLAS_CHECK(rocblas_create_handle(&h));
     rocblas_set_pointer_mode(h, rocblas_pointer_mode_host);
     rocblas_set_stream(h, g.stream);
   }
@@ -36,6 +46,23 @@ inline rocblas_int* dev_info(GpuTaskCtx& g) {
   rocblas_int*& p = infos[(void*)g.stream];
   if (!p) PA_HIP_CHECK(hipMalloc(&p, sizeof(rocblas_int)));
   return p;
+}
+
+// A fresh pool buffer for flow f's tile and, once the kernels that fill it
+// are enqueued, its swap-in as the tile's device copy: an operation that
+// cannot run in place needs no copy back. The old buffer returns to the pool
+// only after the task's kernels complete (the engine's deferred frees).
+inline double* fresh_tile(Task& t, GpuTaskCtx& g, int f) {
+  return (double*)g.engine->dev_alloc(t.flows[f].data->bytes);
+}
+inline void swap_in_tile(Task& t, GpuTaskCtx& g, int f, double* X) {
+  Data* d = t.flows[f].data;
+  {
+    SpinGuard gd(d->lock);
+    g.deferred_frees->emplace_back(d->dev_ptr, d->bytes);
+    d->dev_ptr = X;
+  }
+  t.dev_ptr[f] = X;
 }
 
 }  // namespace pa

@@ -153,10 +153,10 @@ void GpuGraph::launch(int iters) {
 }
 
 GpuGraph::~GpuGraph() {
-  if (exec_) hipGraphExecDestroy(exec_);
-  if (graph_) hipGraphDestroy(graph_);
-  for (auto e : evs_) hipEventDestroy(e);
-  for (auto s : cs_) hipStreamDestroy(s);
+  if (exec_) (void)hipGraphExecDestroy(exec_);
+  if (graph_) (void)hipGraphDestroy(graph_);
+  for (auto e : evs_) (void)hipEventDestroy(e);
+  for (auto s : cs_) (void)hipStreamDestroy(s);
   for (auto& [p, b] : deferred_) eng_->dev_free(p, b);
   for (Data* d : pinned_) eng_->unpin(d);
   for (Task* t : tasks_) t->release();

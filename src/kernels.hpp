@@ -26,6 +26,27 @@ struct TileArgs {
   uint32_t seed = 0;
 };
 
+// The operation shape of a tile chore; the other fields stay zero.
+inline TileArgs tile_args(int m, int n, int k, int ld) {
+  TileArgs a;
+  a.m = m;
+  a.n = n;
+  a.k = k;
+  a.ld = ld;
+  return a;
+}
+
+// Tile (tm, tn) of A for the synthetic fill: its extent and leading
+// dimension, the global index of its first element, the matrix order, seed.
+inline TileArgs fill_args(TiledMatrix& A, int tm, int tn, uint32_t seed) {
+  TileArgs a = tile_args(A.tile_rows(tm), A.tile_cols(tn), 0, A.mb());
+  a.i0 = (int64_t)tm * A.mb();
+  a.j0 = (int64_t)tn * A.nb();
+  a.N = A.m();
+  a.seed = seed;
+  return a;
+}
+
 // Arguments of tc_gemm_nn: C = alpha op(A) B + beta C.
 struct GemmNNArgs {
   int m, n, k, lda, ldb, ldc;
@@ -42,11 +63,47 @@ struct TrsmSolveArgs {
   int unit = 0;   // unit diagonal (LU's L)
 };
 
+// Every task-class id of the process in one place: the id is the key of the
+// trace header's class dictionary (profiling.cpp) and the row of the PINS
+// per-class counters (pins_modules.cpp), so two classes must never share
+// one. Python-defined classes (pybind.cpp) all share TC_PY_TASK; giving each
+// its own id would need dynamic assignment.
+enum TaskClassId : int {
+  // kernels_blas.cpp
+  TC_SPD_FILL = 1, TC_POTRF = 2, TC_TRSM = 3, TC_SYRK = 4, TC_GEMM = 5,
+  TC_TRTRI = 6, TC_TRSM_INV = 7,
+  // kernels_qr.cpp
+  TC_GEQRT = 10, TC_UNMQR = 11, TC_TSQRT = 12, TC_TSMQR = 13,
+  // kernels_bf16.cpp
+  TC_FILL_BF16 = 20, TC_GEMM_BF16 = 21,
+  // kernels_panel.cpp
+  TC_PANEL_FILL = 24, TC_PANEL_FACTOR = 25, TC_PANEL_UPDATE = 26,
+  // kernels_collections.cpp
+  TC_COPY_TILE = 30, TC_SCALE = 31, TC_ADD_TILE = 32, TC_ADD2 = 33,
+  TC_STENCIL3 = 34, TC_REGRID_ZERO = 36, TC_REGRID_PIECE = 37,
+  // kernels_lu.cpp
+  TC_GETRF_NOPIV = 40, TC_LU_TRSM_L = 41, TC_LU_TRSM_U = 42, TC_LU_GEMM = 43,
+  TC_LU_TRTRI = 44, TC_LU_TRSM_L_INV = 45, TC_LU_TRSM_U_INV = 46,
+  // kernels_qr_bcgs.cpp
+  TC_QR_GEMM_TN = 50, TC_QR_ZERO = 51, TC_QR_TRI_TT = 52, TC_QR_GEMM_NN = 53,
+  // kernels_reshape.cpp
+  TC_RESHAPE = 60,
+  // kernels_blas.cpp (gemm_nn, trsm_solve), kernels_collections.cpp (advise)
+  TC_GEMM_NN = 70, TC_ADVISE_PREFETCH = 71, TC_TRSM_SOLVE = 72,
+  // kernels_inv.cpp
+  TC_INV_TRSM_R = 80, TC_TRTRI_INPLACE = 81, TC_SYRK_T = 82, TC_GEMM_TN = 83,
+  TC_TRMM_LLT = 84, TC_LAUUM = 85,
+  // pybind.cpp
+  TC_PY_TASK = 100,
+};
+
 // A task class with a CPU and a GPU incarnation, registered with the
 // profiler under `id` (kernels_blas.cpp). Every kernels_*.cpp builds its
-// classes through this.
+// classes through this; registering an id twice under different names is
+// fatal. `blocking` runs the GPU chore on a worker thread (it may host-sync).
 TaskClass make_tc(const char* name, TaskKind kind, void (*cpu)(Task&),
-                  void (*gpu)(Task&, GpuTaskCtx&), int id);
+                  void (*gpu)(Task&, GpuTaskCtx&), TaskClassId id,
+                  bool blocking = false);
 
 // Registered once; ids stable.
 TaskClass& tc_spd_fill();
@@ -61,6 +118,9 @@ bool gemm_nn_hip();
 
 TaskClass& tc_trtri();
 TaskClass& tc_trsm_inv();
+// The inversion loop of the CPU trtri chores: W's lower triangle <- L^-1
+// for the n x n lower triangular L; nothing above W's diagonal is written.
+void cpu_trtri_lower(int n, const double* L, int ldl, double* W, int ldw);
 TaskClass& tc_geqrt();
 TaskClass& tc_unmqr();
 TaskClass& tc_tsqrt();
@@ -118,6 +178,17 @@ void insert_reduce_sum(Dtd& tp, TiledMatrix& A, TiledMatrix& R);
 // log-depth binary-tree variant (BT_reduction.jdf analog).
 void insert_reduce_sum_tree(Dtd& tp, TiledMatrix& A, TiledMatrix& R);
 void insert_stencil_1d(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
+
+// One triangular sweep of a tiled solve (kernels_solve.cpp): for column tile
+// j of B, solve op(F) Z = B over the first `rows` tile rows of B in place,
+// with the triangular factor in F's leading rows x rows tiles. Each step k
+// is one trsm_solve on the diagonal tile F(k,k) (upper, trans, unit as
+// given) and then the gemm_nn updates B(i,j) -= op(F)(i,k) B(k,j) of the
+// rows still to be solved. {lower, N} and {upper, T} sweep forward (k
+// ascending, i = k+1..), the other two backward (k descending, i = k-1..0).
+// Without trans the update reads tile F(i,k); with it, F(k,i) transposed.
+void insert_tri_sweep(Dtd& tp, TiledMatrix& F, int rows, TiledMatrix& B, int j,
+                      bool upper, bool trans, bool unit);
 void insert_panel_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_potrf_panel(Dtd& tp, TiledMatrix& A);
 

@@ -48,8 +48,14 @@ double time_launches(int iters, F run, hipStream_t stream = nullptr) {
   return now_s() - t0;
 }
 
+// The synthetic SPD fill kernel on a rows x cols block whose first element
+// has the global index (i0, j0): the fill chore's kernel, and the operand
+// fill of the library bench loops (kernels_blas.cpp).
+void launch_spd_fill(double* t, int rows, int cols, int ld, int64_t i0,
+                     int64_t j0, int64_t N, uint32_t seed, hipStream_t s);
+
 // Timed library loops for the A/B against the hand kernels; seconds for
-// `iters` calls (kernels_blas.cpp).
+// `iters` calls (dgemm: kernels_blas.cpp, tn: kernels_inv.cpp).
 double bench_dgemm_rocblas(int m, int n, int k, int iters);
 double bench_dgemm_nn_rocblas(int m, int n, int k, int iters);
 double bench_tn_rocblas(int kind, int m, int n, int k, int iters);

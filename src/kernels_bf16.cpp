@@ -491,10 +491,12 @@ static void launch_gemm_bf16(int m, int n, int k, const void* A, int lda,
                                   : (const void*)k_gemm_bf16_tn_v3;
     static bool attr3 = false;
     if (!attr3) {
-      hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v3,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v4,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      (void)hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v3,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds);
+      (void)hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v4,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds);
       attr3 = true;
     }
     int nbx = m / GB3_BM, nby = n / GB3_BN;
@@ -514,8 +516,9 @@ static void launch_gemm_bf16(int m, int n, int k, const void* A, int lda,
     constexpr size_t lds = 2 * (GB_BM + GB_BN) * GB2_BK * 2;
     static bool attr_set = false;
     if (!attr_set) {
-      hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v2,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      (void)hipFuncSetAttribute((const void*)k_gemm_bf16_tn_v2,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds);
       attr_set = true;
     }
     hipLaunchKernelGGL(k_gemm_bf16_tn_v2, dim3(nbx * nby), dim3(256), lds,
@@ -611,12 +614,12 @@ static void gpu_gemm_bf16(Task& t, GpuTaskCtx& g) {
 
 TaskClass& tc_fill_bf16() {
   static TaskClass tc = make_tc("fill_bf16", TaskKind::GPU, cpu_fill_bf16,
-                                gpu_fill_bf16, 20);
+                                gpu_fill_bf16, TC_FILL_BF16);
   return tc;
 }
 TaskClass& tc_gemm_bf16() {
   static TaskClass tc = make_tc("gemm_bf16", TaskKind::GPU, cpu_gemm_bf16,
-                                gpu_gemm_bf16, 21);
+                                gpu_gemm_bf16, TC_GEMM_BF16);
   return tc;
 }
 

@@ -173,9 +173,8 @@ void cpu_trsm_l_inv(Task& t) {
 void gpu_getrf(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   rocblas_int* dinfo = dev_info(g);
-  PA_CHECK(rocsolver_dgetrf_npvt(blas_handle(g), a.n, a.n,
-                                 (double*)t.dev_ptr[0], a.ld,
-                                 dinfo) == rocblas_status_success);
+  PA_BLAS_CHECK(rocsolver_dgetrf_npvt(blas_handle(g), a.n, a.n,
+                                      (double*)t.dev_ptr[0], a.ld, dinfo));
   // Blocking chore (worker thread): read the info scalar back so a
   // zero/tiny pivot fails as loudly as the CPU reference path does,
   // instead of silently poisoning the trailing matrix with Inf/NaN.
@@ -189,23 +188,21 @@ void gpu_getrf(Task& t, GpuTaskCtx& g) {
 void gpu_trsm_l(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_left,
-                         rocblas_fill_lower, rocblas_operation_none,
-                         rocblas_diagonal_unit, a.m, a.n, &one,
-                         (const double*)t.dev_ptr[0], a.ld,
-                         (double*)t.dev_ptr[1], a.ld) ==
-           rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_left,
+                              rocblas_fill_lower, rocblas_operation_none,
+                              rocblas_diagonal_unit, a.m, a.n, &one,
+                              (const double*)t.dev_ptr[0], a.ld,
+                              (double*)t.dev_ptr[1], a.ld));
 }
 
 void gpu_trsm_u(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_right,
-                         rocblas_fill_upper, rocblas_operation_none,
-                         rocblas_diagonal_non_unit, a.m, a.n, &one,
-                         (const double*)t.dev_ptr[0], a.ld,
-                         (double*)t.dev_ptr[1], a.ld) ==
-           rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dtrsm(blas_handle(g), rocblas_side_right,
+                              rocblas_fill_upper, rocblas_operation_none,
+                              rocblas_diagonal_non_unit, a.m, a.n, &one,
+                              (const double*)t.dev_ptr[0], a.ld,
+                              (double*)t.dev_ptr[1], a.ld));
 }
 
 void gpu_gemm_nn(Task& t, GpuTaskCtx& g) {
@@ -217,12 +214,11 @@ void gpu_gemm_nn(Task& t, GpuTaskCtx& g) {
     return;
   }
   const double mone = -1.0, one = 1.0;
-  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
-                         rocblas_operation_none, a.m, a.n, a.k, &mone,
-                         (const double*)t.dev_ptr[0], a.ld,
-                         (const double*)t.dev_ptr[1], a.ld, &one,
-                         (double*)t.dev_ptr[2], a.ld) ==
-           rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
+                              rocblas_operation_none, a.m, a.n, a.k, &mone,
+                              (const double*)t.dev_ptr[0], a.ld,
+                              (const double*)t.dev_ptr[1], a.ld, &one,
+                              (double*)t.dev_ptr[2], a.ld));
 }
 
 void gpu_lu_trtri(Task& t, GpuTaskCtx& g) {
@@ -231,31 +227,23 @@ void gpu_lu_trtri(Task& t, GpuTaskCtx& g) {
   double* W = (double*)t.dev_ptr[1];
   PA_HIP_CHECK(hipMemsetAsync(W, 0, wd->bytes, g.stream));
   rocblas_handle h = blas_handle(g);
-  PA_CHECK(rocblas_dtrtri(h, rocblas_fill_upper, rocblas_diagonal_non_unit,
-                          a.n, (const double*)t.dev_ptr[0], a.ld, W,
-                          a.n) == rocblas_status_success);
-  PA_CHECK(rocblas_dtrtri(h, rocblas_fill_lower, rocblas_diagonal_unit, a.n,
-                          (const double*)t.dev_ptr[0], a.ld,
-                          W + (size_t)a.n * a.n,
-                          a.n) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dtrtri(h, rocblas_fill_upper, rocblas_diagonal_non_unit,
+                               a.n, (const double*)t.dev_ptr[0], a.ld, W, a.n));
+  PA_BLAS_CHECK(rocblas_dtrtri(h, rocblas_fill_lower, rocblas_diagonal_unit,
+                               a.n, (const double*)t.dev_ptr[0], a.ld,
+                               W + (size_t)a.n * a.n, a.n));
 }
 
 // X = B * Wu into a fresh pool buffer, swapped in as the tile's device
 // copy (no D2D copy — the Cholesky buffer-swap pattern).
 void lu_swap_gemm(Task& t, GpuTaskCtx& g, const double* A0, int lda,
                   const double* B0, int ldb, int m, int n, int k) {
-  Data* bd = t.flows[1].data;
-  double* X = (double*)g.engine->dev_alloc(bd->bytes);
+  double* X = fresh_tile(t, g, 1);
   const double one = 1.0, zero = 0.0;
-  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
-                         rocblas_operation_none, m, n, k, &one, A0, lda, B0,
-                         ldb, &zero, X, m) == rocblas_status_success);
-  {
-    SpinGuard gd(bd->lock);
-    g.deferred_frees->emplace_back(bd->dev_ptr, bd->bytes);
-    bd->dev_ptr = X;
-  }
-  t.dev_ptr[1] = X;
+  PA_BLAS_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
+                              rocblas_operation_none, m, n, k, &one, A0, lda,
+                              B0, ldb, &zero, X, m));
+  swap_in_tile(t, g, 1, X);
 }
 
 void gpu_trsm_u_inv(Task& t, GpuTaskCtx& g) {
@@ -272,44 +260,39 @@ void gpu_trsm_l_inv(Task& t, GpuTaskCtx& g) {
                a.m);
 }
 
-TaskClass make_lu_tc(const char* name, void (*cpu)(Task&),
-                     void (*gpu)(Task&, GpuTaskCtx&), int id,
-                     bool blocking = false) {
-  TaskClass tc = make_tc(name, TaskKind::GPU, cpu, gpu, id);
-  tc.gpu_blocking = blocking;
-  return tc;
-}
-
 TaskClass& tc_getrf() {
-  static TaskClass tc = make_lu_tc("getrf_nopiv", cpu_getrf, gpu_getrf, 40,
-                                   /*blocking=*/true);
+  static TaskClass tc = make_tc("getrf_nopiv", TaskKind::GPU, cpu_getrf,
+                                gpu_getrf, TC_GETRF_NOPIV, /*blocking=*/true);
   return tc;
 }
 TaskClass& tc_lutrsml() {
-  static TaskClass tc = make_lu_tc("lu_trsm_l", cpu_trsm_l, gpu_trsm_l, 41);
+  static TaskClass tc = make_tc("lu_trsm_l", TaskKind::GPU, cpu_trsm_l,
+                                gpu_trsm_l, TC_LU_TRSM_L);
   return tc;
 }
 TaskClass& tc_lutrsmu() {
-  static TaskClass tc = make_lu_tc("lu_trsm_u", cpu_trsm_u, gpu_trsm_u, 42);
+  static TaskClass tc = make_tc("lu_trsm_u", TaskKind::GPU, cpu_trsm_u,
+                                gpu_trsm_u, TC_LU_TRSM_U);
   return tc;
 }
 TaskClass& tc_lugemm() {
-  static TaskClass tc = make_lu_tc("lu_gemm", cpu_gemm_nn, gpu_gemm_nn, 43);
+  static TaskClass tc = make_tc("lu_gemm", TaskKind::GPU, cpu_gemm_nn,
+                                gpu_gemm_nn, TC_LU_GEMM);
   return tc;
 }
 TaskClass& tc_lu_trtri() {
-  static TaskClass tc =
-      make_lu_tc("lu_trtri", cpu_lu_trtri, gpu_lu_trtri, 44);
+  static TaskClass tc = make_tc("lu_trtri", TaskKind::GPU, cpu_lu_trtri,
+                                gpu_lu_trtri, TC_LU_TRTRI);
   return tc;
 }
 TaskClass& tc_lutrsml_inv() {
-  static TaskClass tc =
-      make_lu_tc("lu_trsm_l_inv", cpu_trsm_l_inv, gpu_trsm_l_inv, 45);
+  static TaskClass tc = make_tc("lu_trsm_l_inv", TaskKind::GPU, cpu_trsm_l_inv,
+                                gpu_trsm_l_inv, TC_LU_TRSM_L_INV);
   return tc;
 }
 TaskClass& tc_lutrsmu_inv() {
-  static TaskClass tc =
-      make_lu_tc("lu_trsm_u_inv", cpu_trsm_u_inv, gpu_trsm_u_inv, 46);
+  static TaskClass tc = make_tc("lu_trsm_u_inv", TaskKind::GPU, cpu_trsm_u_inv,
+                                gpu_trsm_u_inv, TC_LU_TRSM_U_INV);
   return tc;
 }
 
@@ -334,28 +317,22 @@ void insert_getrf_nopiv(Dtd& tp, TiledMatrix& A) {
     Wc->set_rank_table(std::move(wranks));
     tp.own(Wc);
   }
+  // every tile is a whole nb x nb one
+  TileArgs d = tile_args(nb, nb, 0, ld);
+  TileArgs upd = tile_args(nb, nb, nb, ld);
   for (int k = 0; k < T; k++) {
-    TileArgs a;
-    a.n = nb;
-    a.ld = ld;
     {
-      TileArgs d = a;
-      d.m = nb;
       Dtd::FlowSpec f[] = {{A.tile(k, k), ACCESS_INOUT}};
       tp.insert(&tc_getrf(), &d, sizeof(d), f, 1, PANEL + 1,
                 A.rank_of(k, k));
     }
     if (inv && k + 1 < T) {
-      TileArgs d = a;
-      d.m = nb;
       Dtd::FlowSpec f[] = {{A.tile(k, k), ACCESS_IN},
                            {Wc->tile(k, 0), ACCESS_OUT}};
       tp.insert(&tc_lu_trtri(), &d, sizeof(d), f, 2, PANEL,
                 A.rank_of(k, k));
     }
     for (int n = k + 1; n < T; n++) {
-      TileArgs d = a;
-      d.m = nb;
       if (inv) {
         Dtd::FlowSpec f[] = {{Wc->tile(k, 0), ACCESS_IN},
                              {A.tile(k, n), ACCESS_INOUT}};
@@ -369,8 +346,6 @@ void insert_getrf_nopiv(Dtd& tp, TiledMatrix& A) {
       }
     }
     for (int m = k + 1; m < T; m++) {
-      TileArgs d = a;
-      d.m = nb;
       if (inv) {
         Dtd::FlowSpec f[] = {{Wc->tile(k, 0), ACCESS_IN},
                              {A.tile(m, k), ACCESS_INOUT}};
@@ -385,13 +360,10 @@ void insert_getrf_nopiv(Dtd& tp, TiledMatrix& A) {
     }
     for (int m = k + 1; m < T; m++)
       for (int n = k + 1; n < T; n++) {
-        TileArgs d = a;
-        d.m = nb;
-        d.k = nb;
         Dtd::FlowSpec f[] = {{A.tile(m, k), ACCESS_IN},
                              {A.tile(k, n), ACCESS_IN},
                              {A.tile(m, n), ACCESS_INOUT}};
-        tp.insert(&tc_lugemm(), &d, sizeof(d), f, 3, -(n - k) * 4,
+        tp.insert(&tc_lugemm(), &upd, sizeof(upd), f, 3, -(n - k) * 4,
                   A.rank_of(m, n));
       }
   }

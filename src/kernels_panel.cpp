@@ -92,14 +92,14 @@ static void gpu_panel_factor(Task& t, GpuTaskCtx& g) {
     int rest = nb - j - jb;
     if (rest > 0) {
       double* Aij = diag + (size_t)j * ld + j + jb;
-      PA_CHECK(rocblas_dtrsm(h, rocblas_side_right, rocblas_fill_lower,
-                             rocblas_operation_transpose,
-                             rocblas_diagonal_non_unit, rest, jb, &one, Ajj,
-                             (int)ld, Aij, (int)ld) == rocblas_status_success);
+      PA_BLAS_CHECK(rocblas_dtrsm(h, rocblas_side_right, rocblas_fill_lower,
+                                  rocblas_operation_transpose,
+                                  rocblas_diagonal_non_unit, rest, jb, &one,
+                                  Ajj, (int)ld, Aij, (int)ld));
       double* Att = diag + (size_t)(j + jb) * ld + j + jb;
-      PA_CHECK(rocblas_dsyrk(h, rocblas_fill_lower, rocblas_operation_none,
-                             rest, jb, &mone, Aij, (int)ld, &one, Att,
-                             (int)ld) == rocblas_status_success);
+      PA_BLAS_CHECK(rocblas_dsyrk(h, rocblas_fill_lower, rocblas_operation_none,
+                                  rest, jb, &mone, Aij, (int)ld, &one, Att,
+                                  (int)ld));
     }
   }
   const int64_t below = a.m - nb;  // rows under the diagonal block
@@ -113,13 +113,13 @@ static void gpu_panel_factor(Task& t, GpuTaskCtx& g) {
     g.deferred_frees->emplace_back(W, (size_t)nb * nb * 8);
     g.deferred_frees->emplace_back(X, (size_t)below * nb * 8);
     PA_HIP_CHECK(hipMemsetAsync(W, 0, (size_t)nb * nb * 8, g.stream));
-    PA_CHECK(rocblas_dtrtri(h, rocblas_fill_lower, rocblas_diagonal_non_unit,
-                            nb, diag, (int)ld, W, nb) == rocblas_status_success);
+    PA_BLAS_CHECK(rocblas_dtrtri(h, rocblas_fill_lower,
+                                 rocblas_diagonal_non_unit, nb, diag, (int)ld,
+                                 W, nb));
     const double zero = 0.0;
-    PA_CHECK(rocblas_dgemm(h, rocblas_operation_none,
-                           rocblas_operation_transpose, (int)below, nb, nb,
-                           &one, B, (int)ld, W, nb, &zero, X,
-                           (int)below) == rocblas_status_success);
+    PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none,
+                                rocblas_operation_transpose, (int)below, nb, nb,
+                                &one, B, (int)ld, W, nb, &zero, X, (int)below));
     PA_HIP_CHECK(hipMemcpy2DAsync(B, (size_t)ld * 8, X, (size_t)below * 8,
                                   (size_t)below * 8, nb,
                                   hipMemcpyDeviceToDevice, g.stream));
@@ -158,10 +158,10 @@ static void gpu_panel_update(Task& t, GpuTaskCtx& g) {
   const double* A1 = (const double*)t.dev_ptr[0] + a.i0;  // rows n*nb..
   const double* A2 = (const double*)t.dev_ptr[0] + a.i0;  // top nb_n rows
   double* C = (double*)t.dev_ptr[1] + a.i0;
-  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
-                         rocblas_operation_transpose, (int)a.m, a.n, a.k,
-                         &mone, A1, (int)ld, A2, (int)ld, &one, C,
-                         (int)ld) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
+                              rocblas_operation_transpose, (int)a.m, a.n, a.k,
+                              &mone, A1, (int)ld, A2, (int)ld, &one, C,
+                              (int)ld));
 }
 
 static void cpu_panel_update(Task& t) {
@@ -183,19 +183,20 @@ static void cpu_panel_update(Task& t) {
 
 TaskClass& tc_panel_fill() {
   static TaskClass tc =
-      make_tc("panel_fill", TaskKind::GPU, cpu_panel_fill, gpu_panel_fill, 40);
+      make_tc("panel_fill", TaskKind::GPU, cpu_panel_fill, gpu_panel_fill,
+              TC_PANEL_FILL);
   return tc;
 }
 TaskClass& tc_panel_factor() {
   static TaskClass tc =
       make_tc("panel_factor", TaskKind::GPU, cpu_panel_factor,
-              gpu_panel_factor, 41);
+              gpu_panel_factor, TC_PANEL_FACTOR);
   return tc;
 }
 TaskClass& tc_panel_update() {
   static TaskClass tc =
       make_tc("panel_update", TaskKind::GPU, cpu_panel_update,
-              gpu_panel_update, 42);
+              gpu_panel_update, TC_PANEL_UPDATE);
   return tc;
 }
 

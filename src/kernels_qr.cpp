@@ -331,18 +331,17 @@ static void larfb_gemm(GpuTaskCtx& g, int m, int n, int k, const double* A,
                      m, k, lda, m);
   const double one = 1.0, zero = 0.0, mone = -1.0;
   // W = V^T C
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, k, n, m, &one, V, m, C, ldc,
-                         &zero, W, k) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                              rocblas_operation_none, k, n, m, &one, V, m, C,
+                              ldc, &zero, W, k));
   // W = T^T W  (T upper-triangular, stored dense with zero lower)
   double* W2 = qr_scratch(g, slot + 2, (size_t)k * n * 8);
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, k, n, k, &one, T, ldt, W, k,
-                         &zero, W2, k) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                              rocblas_operation_none, k, n, k, &one, T, ldt, W,
+                              k, &zero, W2, k));
   // C -= V W2
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
-                         m, n, k, &mone, V, m, W2, k, &one, C,
-                         ldc) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
+                              m, n, k, &mone, V, m, W2, k, &one, C, ldc));
 }
 
 // ---------------------------------------------------------- hand panel QR
@@ -1162,10 +1161,9 @@ static void qr_larfb_trailing(GpuTaskCtx& g, double* A, int m, int ld, int p,
   double* G = qr_scratch(g, QR_SLOT_G128, (size_t)128 * 128 * 8);
   hipLaunchKernelGGL(k_unitlow, grid1d(prows * pc), dim3(256), 0, g.stream,
                      V, panel, prows, pc, ld, prows);
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, pc, pc, prows, &one, V,
-                         prows, V, prows, &zero, G,
-                         pc) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                              rocblas_operation_none, pc, pc, prows, &one, V,
+                              prows, V, prows, &zero, G, pc));
   double* T128 = qr_scratch(g, QR_SLOT_T128, (size_t)128 * 128 * 8);
   PA_HIP_CHECK(hipMemsetAsync(T128, 0, (size_t)pc * pc * 8, g.stream));
   hipLaunchKernelGGL(k_larft_diag, dim3(1), dim3(128), 0, g.stream, G, pc,
@@ -1214,23 +1212,23 @@ static void qr_factor_hand(GpuTaskCtx& g, double* A, int m, int k, int ld,
   double* G = qr_scratch(g, QR_SLOT_G, (size_t)k * k * 8);
   hipLaunchKernelGGL(k_unitlow, grid1d(m * k), dim3(256), 0, g.stream, V, A,
                      m, k, ld, m);
-  PA_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
-                         rocblas_operation_none, k, k, m, &one, V, m, V, m,
-                         &zero, G, k) == rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_transpose,
+                              rocblas_operation_none, k, k, m, &one, V, m, V, m,
+                              &zero, G, k));
   hipLaunchKernelGGL(k_larft_diag, dim3((k + 127) / 128), dim3(128), 0,
                      g.stream, G, k, tau, T, ldt, k);
   double* X = qr_scratch(g, QR_SLOT_X, (size_t)k * 128 * 8);
   for (int b = 128; b < k; b += 128) {
     int bc2 = std::min(128, k - b);
     // X = T(0:b,0:b) * G(0:b, b:b+bc)
-    PA_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
-                           b, bc2, b, &one, T, ldt, G + (size_t)b * k, k,
-                           &zero, X, b) == rocblas_status_success);
+    PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none,
+                                rocblas_operation_none, b, bc2, b, &one, T, ldt,
+                                G + (size_t)b * k, k, &zero, X, b));
     // T(0:b, blk) = -X * T_blk
-    PA_CHECK(rocblas_dgemm(h, rocblas_operation_none, rocblas_operation_none,
-                           b, bc2, bc2, &mone, X, b,
-                           T + (size_t)b * ldt + b, ldt, &zero,
-                           T + (size_t)b * ldt, ldt) == rocblas_status_success);
+    PA_BLAS_CHECK(rocblas_dgemm(h, rocblas_operation_none,
+                                rocblas_operation_none, b, bc2, bc2, &mone, X,
+                                b, T + (size_t)b * ldt + b, ldt, &zero,
+                                T + (size_t)b * ldt, ldt));
   }
 }
 
@@ -1241,10 +1239,10 @@ static void qr_factor_rocsolver(GpuTaskCtx& g, double* A, int m, int k,
   double* tau = qr_scratch(g, QR_SLOT_TAU, (size_t)k * 8);
   rocblas_handle h = blas_handle(g);
   PA_HIP_CHECK(hipMemsetAsync(T, 0, t_bytes, g.stream));
-  PA_CHECK(rocsolver_dgeqrf(h, m, k, A, ld, tau) == rocblas_status_success);
-  PA_CHECK(rocsolver_dlarft(h, rocblas_forward_direction,
-                            rocblas_column_wise, m, k, A, ld, tau, T,
-                            ldt) == rocblas_status_success);
+  PA_BLAS_CHECK(rocsolver_dgeqrf(h, m, k, A, ld, tau));
+  PA_BLAS_CHECK(rocsolver_dlarft(h, rocblas_forward_direction,
+                                 rocblas_column_wise, m, k, A, ld, tau, T,
+                                 ldt));
 }
 
 static void gpu_geqrt(Task& t, GpuTaskCtx& g) {
@@ -1313,7 +1311,8 @@ TaskClass& tc_geqrt() {
   // panel kernel), so it pipelines through the manager like any chore.
   // PARSEC_MCA_qr_blocking_panels=0 restores manager execution.
   static TaskClass tc = [] {
-    TaskClass c = make_tc("geqrt", TaskKind::GPU, cpu_geqrt, gpu_geqrt, 10);
+    TaskClass c = make_tc("geqrt", TaskKind::GPU, cpu_geqrt, gpu_geqrt,
+                          TC_GEQRT);
     bool rocs = param_str("chore_qr", "hand") == "rocsolver";
     c.gpu_blocking = rocs && param_int("qr_blocking_panels", 1) != 0;
     return c;
@@ -1322,12 +1321,13 @@ TaskClass& tc_geqrt() {
 }
 TaskClass& tc_unmqr() {
   static TaskClass tc =
-      make_tc("unmqr", TaskKind::GPU, cpu_unmqr, gpu_unmqr, 11);
+      make_tc("unmqr", TaskKind::GPU, cpu_unmqr, gpu_unmqr, TC_UNMQR);
   return tc;
 }
 TaskClass& tc_tsqrt() {
   static TaskClass tc = [] {
-    TaskClass c = make_tc("tsqrt", TaskKind::GPU, cpu_tsqrt, gpu_tsqrt, 12);
+    TaskClass c = make_tc("tsqrt", TaskKind::GPU, cpu_tsqrt, gpu_tsqrt,
+                          TC_TSQRT);
     bool rocs = param_str("chore_qr", "hand") == "rocsolver";
     c.gpu_blocking = rocs && param_int("qr_blocking_panels", 1) != 0;
     return c;
@@ -1336,7 +1336,7 @@ TaskClass& tc_tsqrt() {
 }
 TaskClass& tc_tsmqr() {
   static TaskClass tc =
-      make_tc("tsmqr", TaskKind::GPU, cpu_tsmqr, gpu_tsmqr, 13);
+      make_tc("tsmqr", TaskKind::GPU, cpu_tsmqr, gpu_tsmqr, TC_TSMQR);
   return tc;
 }
 
@@ -1521,23 +1521,9 @@ void insert_gels(Dtd& tp, TiledMatrix& A, TiledMatrix& B) {
            "insert_gels: fp64 matrices of one context");
   insert_qr_sweep(tp, A, &B);
   // backward: R X = (Q^T B)[0:N], R upper non-unit
-  const int nb = A.nb(), ld = A.mb();
   for (int j = 0; j < B.nt(); j++)
-    for (int k = A.nt() - 1; k >= 0; k--) {
-      TrsmSolveArgs a{nb, B.tile_cols(j), ld, ld, 0};
-      a.upper = 1;
-      Dtd::FlowSpec f[] = {{A.tile(k, k), ACCESS_IN},
-                           {B.tile(k, j), ACCESS_INOUT}};
-      tp.insert(&tc_trsm_solve(), &a, sizeof(a), f, 2, (1 << 20),
-                B.rank_of(k, j));
-      for (int i = k - 1; i >= 0; i--) {
-        GemmNNArgs a2{nb, B.tile_cols(j), nb, ld, ld, ld, -1.0, 1.0};
-        Dtd::FlowSpec f2[] = {{A.tile(i, k), ACCESS_IN},
-                              {B.tile(k, j), ACCESS_IN},
-                              {B.tile(i, j), ACCESS_INOUT}};
-        tp.insert(&tc_gemm_nn(), &a2, sizeof(a2), f2, 3, 0, B.rank_of(i, j));
-      }
-    }
+    insert_tri_sweep(tp, A, A.nt(), B, j, /*upper=*/true, /*trans=*/false,
+                     /*unit=*/false);
 }
 
 // Standalone micro-benchmark of the TS/tile panel factorization path, by
@@ -1562,8 +1548,7 @@ double bench_qr_factor(int m, int k, int ts_split, int iters, int mode) {
     if (mode == QR_BENCH_FULL) {
       qr_factor_hand(g, dA.p, m, k, m, dT.p, k, ts_split, cfg);
     } else if (mode == QR_BENCH_ROCSOLVER) {
-      PA_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA.p, m, tau) ==
-               rocblas_status_success);
+      PA_BLAS_CHECK(rocsolver_dgeqrf(blas_handle(g), m, k, dA.p, m, tau));
     } else {
       for (int p = 0; p < k; p += 128) {
         const int pc = std::min(128, k - p);

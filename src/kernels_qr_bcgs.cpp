@@ -56,12 +56,11 @@ void cpu_gemm_tn_acc(Task& t) {
 void gpu_gemm_tn_acc(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double one = 1.0;
-  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_transpose,
-                         rocblas_operation_none, a.n, a.n, a.m, &one,
-                         (const double*)t.dev_ptr[0], a.ld,
-                         (const double*)t.dev_ptr[1], a.ld, &one,
-                         (double*)t.dev_ptr[2], a.n) ==
-           rocblas_status_success);
+  PA_BLAS_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_transpose,
+                              rocblas_operation_none, a.n, a.n, a.m, &one,
+                              (const double*)t.dev_ptr[0], a.ld,
+                              (const double*)t.dev_ptr[1], a.ld, &one,
+                              (double*)t.dev_ptr[2], a.n));
 }
 
 // ---- zero an nb x nb workspace tile ----
@@ -139,35 +138,33 @@ void cpu_gemm_nn_sub(Task& t) {
 void gpu_gemm_nn_sub(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const double mone = -1.0, one = 1.0;
-  PA_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
-                         rocblas_operation_none, a.m, a.n, a.k, &mone,
-                         (const double*)t.dev_ptr[0], a.ld,
-                         (const double*)t.dev_ptr[1], a.k, &one,
-                         (double*)t.dev_ptr[2], a.ld) ==
-           rocblas_status_success);
-}
-
-TaskClass make_bc_tc(const char* name, void (*cpu)(Task&),
-                     void (*gpu)(Task&, GpuTaskCtx&), int id) {
-  return make_tc(name, TaskKind::GPU, cpu, gpu, id);
+  PA_BLAS_CHECK(rocblas_dgemm(blas_handle(g), rocblas_operation_none,
+                              rocblas_operation_none, a.m, a.n, a.k, &mone,
+                              (const double*)t.dev_ptr[0], a.ld,
+                              (const double*)t.dev_ptr[1], a.k, &one,
+                              (double*)t.dev_ptr[2], a.ld));
 }
 
 TaskClass& tc_gemm_tn_acc() {
   static TaskClass tc =
-      make_bc_tc("qr_gemm_tn", cpu_gemm_tn_acc, gpu_gemm_tn_acc, 50);
+      make_tc("qr_gemm_tn", TaskKind::GPU, cpu_gemm_tn_acc, gpu_gemm_tn_acc,
+              TC_QR_GEMM_TN);
   return tc;
 }
 TaskClass& tc_zero_tile() {
-  static TaskClass tc = make_bc_tc("qr_zero", cpu_zero_tile, gpu_zero_tile, 51);
+  static TaskClass tc = make_tc("qr_zero", TaskKind::GPU, cpu_zero_tile,
+                                gpu_zero_tile, TC_QR_ZERO);
   return tc;
 }
 TaskClass& tc_tri_tt() {
-  static TaskClass tc = make_bc_tc("qr_tri_tt", cpu_tri_tt, gpu_tri_tt, 52);
+  static TaskClass tc = make_tc("qr_tri_tt", TaskKind::GPU, cpu_tri_tt,
+                                gpu_tri_tt, TC_QR_TRI_TT);
   return tc;
 }
 TaskClass& tc_gemm_nn_sub() {
   static TaskClass tc =
-      make_bc_tc("qr_gemm_nn", cpu_gemm_nn_sub, gpu_gemm_nn_sub, 53);
+      make_tc("qr_gemm_nn", TaskKind::GPU, cpu_gemm_nn_sub, gpu_gemm_nn_sub,
+              TC_QR_GEMM_NN);
   return tc;
 }
 

@@ -19,7 +19,6 @@
 #include "device_gpu.hpp"
 #include "dtd.hpp"
 #include "kernels.hpp"
-#include "profiling.hpp"
 
 namespace pa {
 
@@ -168,16 +167,8 @@ void gpu_reshape(Task& t, GpuTaskCtx& g) {
 }  // namespace
 
 TaskClass& tc_reshape() {
-  static TaskClass tc = [] {
-    Profiler::inst().register_class(60, "reshape");
-    TaskClass c;
-    c.name = "reshape";
-    c.kind = TaskKind::GPU;
-    c.cpu_hook = cpu_reshape;
-    c.gpu_hook = gpu_reshape;
-    c.id = 60;
-    return c;
-  }();
+  static TaskClass tc =
+      make_tc("reshape", TaskKind::GPU, cpu_reshape, gpu_reshape, TC_RESHAPE);
   return tc;
 }
 

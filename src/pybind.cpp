@@ -92,7 +92,7 @@ TaskClass& py_task_class() {
     c.kind = TaskKind::CPU;
     c.cpu_hook = py_task_hook;
     c.destruct = py_task_destruct;
-    c.id = 100;
+    c.id = TC_PY_TASK;
     return c;
   }();
   return tc;

@@ -296,7 +296,7 @@ void Taskpool::wait_dynamic() {
     v[1] = ce->ctl_sent();
     v[2] = ce->ctl_recvd();
   };
-  ce->set_sys_handler([this, st, ce, rank, triple, epoch](
+  ce->set_sys_handler([st, ce, triple, epoch](
                           int src, uint32_t tag, const std::string& pl) {
     if (tag == TD_PROBE) {
       uint64_t rep[5];

@@ -406,3 +406,129 @@ print("MT_OK", rank)
                           str(tmp_path / "merged.json"))
     evs = _json.load(open(out))["traceEvents"]
     assert n > 10 and {e.get("pid") for e in evs} >= {0, 10}
+
+
+def test_task_class_ids_unique(tmp_path):
+    """Every task class a process registers has an id of its own: the trace
+    header's class dictionary (written as registered, so a shared id shows
+    as a duplicate key) has none twice. Reduce + stencil and panel Cholesky
+    + LU are the pairs that used to share ids. add2 is the tree reduction's
+    class, so insert_reduce_sum_tree runs next to insert_reduce_sum."""
+    import json
+    trace = tmp_path / "trace"
+    code = f"""
+import sys
+sys.path.insert(0, {REPO!r})
+import numpy as np
+import parsec_amd as pm
+pm.param_set("profile_filename", {str(trace)!r})
+ctx = pm.Context(nworkers=2, rank=0, world=1, gpu=-2)
+def mat(m, n, mb=64, nb=64):
+    return pm.TiledMatrix(ctx, m, n, mb, nb, 1, 1)
+def run(fn):
+    tp = pm.Dtd(ctx)
+    fn(tp)
+    tp.wait()
+A, R = mat(128, 128), mat(64, 64)
+run(lambda tp: pm.insert_full_fill(tp, A, 3))
+R.tile_numpy_set(0, 0, np.zeros((64, 64)))
+run(lambda tp: pm.insert_reduce_sum(tp, A, R))
+run(lambda tp: pm.insert_reduce_sum_tree(tp, A, R))
+S, D = mat(128, 1, 64, 1), mat(128, 1, 64, 1)
+for t in range(2):
+    S.tile_numpy_set(t, 0, np.ones((64, 1)))
+run(lambda tp: pm.insert_stencil_1d(tp, S, D))
+P = mat(128, 128, 128, 64)
+run(lambda tp: (pm.insert_panel_fill(tp, P, 1), pm.insert_potrf_panel(tp, P)))
+# diagonally dominant, so LU without pivoting is safe
+L, B = mat(128, 128), mat(128, 64)
+run(lambda tp: (pm.insert_spd_fill(tp, L, 2), pm.insert_full_fill(tp, B, 5)))
+L.tile_numpy_set(0, 1, L.tile_numpy(1, 0).T.copy())
+run(lambda tp: (pm.insert_getrf_nopiv(tp, L), pm.insert_getrs_nopiv(tp, L, B)))
+C = mat(128, 128)
+run(lambda tp: (pm.insert_spd_fill(tp, C, 4), pm.insert_poinv(tp, C)))
+run(lambda tp: (pm.insert_spd_fill(tp, C, 4), pm.insert_posv(tp, C, B)))
+run(lambda tp: (pm.insert_full_fill(tp, A, 3), pm.insert_gels(tp, A, B)))
+del A, R, S, D, P, L, B, C, ctx
+print("IDS_OK")
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True,
+                       text=True, timeout=120)
+    assert "IDS_OK" in r.stdout, r.stdout + r.stderr
+    with open(str(trace) + ".0", "rb") as f:
+        f.readline()  # magic
+        header = dict(json.loads(f.readline(), object_pairs_hook=list))
+    ids = [k for k, _ in header["classes"]]
+    names = [v for _, v in header["classes"]]
+    twice = sorted({(k, v) for k, v in header["classes"] if ids.count(k) > 1})
+    assert not twice, f"task-class ids registered twice: {twice}"
+    for name in ("add2", "stencil3", "panel_factor", "getrf_nopiv"):
+        assert name in names, (name, names)
+
+
+def test_solve_sweep_insertion_order(tmp_path):
+    """The four solves built on the shared triangular sweep insert their
+    trsm_solve / gemm_nn tasks in the documented order: for each column tile
+    j of B, a forward sweep is k ascending (solve, then updates i = k+1..),
+    a backward sweep k descending (solve, then updates i = k-1..0). DTD
+    derives dependencies from insertion order, so the order is the contract;
+    the numerics tests pin the tile indices."""
+    import re
+    dot = tmp_path / "dag.dot"
+    code = f"""
+import sys
+sys.path.insert(0, {REPO!r})
+import parsec_amd as pm
+pm.param_set("profile_dot", {str(dot)!r})
+ctx = pm.Context(nworkers=2, rank=0, world=1, gpu=-2)
+def mat(m, n):
+    return pm.TiledMatrix(ctx, m, n, 32, 32, 1, 1)
+def run(fn):
+    tp = pm.Dtd(ctx)
+    fn(tp)
+    tp.wait()
+A, B, R, X = mat(96, 96), mat(96, 64), mat(96, 96), mat(96, 64)
+def fill(tp):
+    pm.insert_spd_fill(tp, A, 1)
+    pm.insert_full_fill(tp, B, 5)
+run(fill)
+for i in range(3):
+    for j in range(i):
+        A.tile_numpy_set(j, i, A.tile_numpy(i, j).T.copy())
+run(lambda tp: pm.insert_potrs(tp, A, B))
+run(fill)
+run(lambda tp: pm.insert_getrs_nopiv(tp, A, B))
+run(fill)
+run(lambda tp: pm.insert_gels_bcgs(tp, A, R, B, X))
+run(fill)
+run(lambda tp: pm.insert_gels(tp, A, B))
+del A, B, R, X, ctx
+print("ORDER_OK")
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True,
+                       text=True, timeout=120)
+    assert "ORDER_OK" in r.stdout, r.stdout + r.stderr
+    got = []
+    for line in open(str(dot) + ".0"):
+        m = re.search(r'\[label="(\w+)\(\d+\)"\]', line)
+        if m and m.group(1) in ("trsm_solve", "gemm_nn"):
+            got.append(m.group(1))
+
+    T, NJ = 3, 2
+
+    def forward():
+        return sum((["trsm_solve"] + ["gemm_nn"] * len(range(k + 1, T))
+                    for k in range(T)), [])
+
+    def backward():
+        return sum((["trsm_solve"] + ["gemm_nn"] * len(range(k - 1, -1, -1))
+                    for k in range(T - 1, -1, -1)), [])
+
+    potrs = sum((forward() + backward() for _ in range(NJ)), [])
+    getrs = potrs
+    # gels_bcgs: X = Q^T B is a gemm_nn chain over (k, j, i), then one
+    # backward sweep per j; gels: one backward sweep per j
+    bcgs = ["gemm_nn"] * (T * NJ * T) + sum((backward() for _ in range(NJ)), [])
+    gels = sum((backward() for _ in range(NJ)), [])
+    want = potrs + getrs + bcgs + gels
+    assert got == want, (len(got), len(want), got)
