@@ -138,7 +138,11 @@ void insert_geqrf(Dtd& tp, TiledMatrix& A);
 void insert_geqrf_bcgs(Dtd& tp, TiledMatrix& A, TiledMatrix& R);
 void insert_getrf_nopiv(Dtd& tp, TiledMatrix& A);
 void insert_fill_bf16(Dtd& tp, TiledMatrix& A, uint32_t seed);
-void insert_gemm_bf16(Dtd& tp, TiledMatrix& At, TiledMatrix& B, TiledMatrix& C);
+// C = op(A) op(B), bf16 in, fp32 out. transa "T": A is K x M, "N": M x K;
+// transb "N": B is K x N, "T": N x K (kernels_bf16.cpp).
+void insert_gemm_bf16(Dtd& tp, TiledMatrix& A, TiledMatrix& B, TiledMatrix& C,
+                      const std::string& transa = "T",
+                      const std::string& transb = "N");
 void insert_redistribute(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_reduce_axis(Dtd& tp, TiledMatrix& A, TiledMatrix& R, int axis);
 void insert_band_to_rect(Dtd& tp, TiledMatrix& S, TiledMatrix& D);

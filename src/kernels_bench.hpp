@@ -61,10 +61,14 @@ double bench_dgemm_nn_rocblas(int m, int n, int k, int iters);
 double bench_tn_rocblas(int kind, int m, int n, int k, int iters);
 
 // bf16 GEMM: TFLOP/s of the kernel, and its host-memory test entry
-// (kernels_bf16.cpp).
-double bench_gemm_bf16(int m, int n, int k, int iters);
+// (kernels_bf16.cpp). a_mmajor: A is m x k col-major instead of k x m;
+// b_nmajor: B is n x k col-major instead of k x n.
+double bench_gemm_bf16(int m, int n, int k, int iters, bool a_mmajor = false,
+                       bool b_nmajor = false);
 void test_gemm_bf16_hip(int m, int n, int k, const uint16_t* A,
-                        const uint16_t* B, float* C);
+                        const uint16_t* B, float* C, bool a_mmajor = false,
+                        bool b_nmajor = false, int lda = 0, int ldb = 0,
+                        int accum = 1);
 
 // What bench_qr_factor times (kernels_qr.cpp); seconds for `iters`
 // factorizations of an m x k tile.

@@ -18,6 +18,7 @@
 #include "device_gpu.hpp"
 #include "kernels.hpp"
 #include "kernels_bench.hpp"
+#include "kernels_bf16.hpp"
 #include "profiling.hpp"
 
 namespace pa {
@@ -26,20 +27,10 @@ namespace pa {
 // from applications/cuBLAS); this bf16 MFMA tile-GEMM is the
 // BASELINE.json config-5 headline app, written CDNA4-first.
 
-typedef __bf16 bf16;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 #define GB_BM 128
 #define GB_BN 128
 #define GB_BK 32
 #define GB_PAD 8  // bf16 elements of row padding (16 B): bank de-phasing
-
-__device__ __forceinline__ int bf_swz(int id, int nwg) {
-  int q = nwg >> 3, r = nwg & 7;
-  int xcd = id & 7, pos = id >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
 
 __launch_bounds__(256)
 __global__ void k_gemm_bf16_tn(int m, int n, int k,
@@ -483,7 +474,13 @@ __global__ void k_gemm_bf16_tn_v4(int m, int n, int k,
 
 static void launch_gemm_bf16(int m, int n, int k, const void* A, int lda,
                              const void* B, int ldb, float* C, int ldc,
-                             hipStream_t stream, int accum = 1) {
+                             hipStream_t stream, int accum = 1,
+                             bool a_mmajor = false, bool b_nmajor = false) {
+  if (a_mmajor || b_nmajor) {
+    launch_gemm_bf16_nx(m, n, k, A, lda, B, ldb, C, ldc, stream, accum,
+                        a_mmajor, b_nmajor);
+    return;
+  }
   if (m % GB3_BM == 0 && n % GB3_BN == 0 && k % GB3_KH == 0 && k >= 4 * GB3_KH) {
     constexpr size_t lds = 4 * (GB3_BM + GB3_BN) * GB3_KH * 2;
     int variant = (int)param_int("bf16_kernel", 3);
@@ -586,6 +583,11 @@ static void gpu_fill_bf16(Task& t, GpuTaskCtx& g) {
 // cross-checks, so both hash tile-local index + per-tile seed.
 
 // ------------------------------------------------------------------ chores
+// TileArgs of a gemm_bf16 task: m, n, k; ld = lda, i0 = ldb; j0 = the
+// accumulate flag; seed carries the operand layouts (0 = TN).
+constexpr uint32_t GB_A_MMAJOR = 1;  // transa = "N": A tile is m x k col-major
+constexpr uint32_t GB_B_NMAJOR = 2;  // transb = "T": B tile is n x k col-major
+
 static void cpu_gemm_bf16(Task& t) {
   const TileArgs& a = t.arg<TileArgs>();
   const int accum = (int)a.j0;
@@ -593,13 +595,19 @@ static void cpu_gemm_bf16(Task& t) {
   const uint16_t* B = (const uint16_t*)t.flows[1].data->pull_to_host();
   Data* cd = t.flows[2].data;
   float* C = accum ? (float*)cd->pull_to_host() : (float*)cd->ensure_host();
-  const int m = a.m, n = a.n, kk = a.k, lda = a.ld;
+  const int m = a.m, n = a.n, kk = a.k;
+  const size_t lda = a.ld, ldb = (size_t)a.i0;
   const int ldc = cd->coll->mb();
+  // element strides of A(i, p) and B(p, j) along (row, K)
+  const size_t ai = a.seed & GB_A_MMAJOR ? 1 : lda;
+  const size_t ap = a.seed & GB_A_MMAJOR ? lda : 1;
+  const size_t bj = a.seed & GB_B_NMAJOR ? 1 : ldb;
+  const size_t bp = a.seed & GB_B_NMAJOR ? ldb : 1;
   for (int j = 0; j < n; j++)
     for (int i = 0; i < m; i++) {
       float s = 0;
       for (int p = 0; p < kk; p++)
-        s += bf2f(A[(size_t)i * lda + p]) * bf2f(B[(size_t)j * lda + p]);
+        s += bf2f(A[i * ai + p * ap]) * bf2f(B[j * bj + p * bp]);
       C[(size_t)j * ldc + i] = accum ? C[(size_t)j * ldc + i] + s : s;
     }
   cd->written_on(false);
@@ -608,8 +616,9 @@ static void cpu_gemm_bf16(Task& t) {
 static void gpu_gemm_bf16(Task& t, GpuTaskCtx& g) {
   const TileArgs& a = t.arg<TileArgs>();
   const int ldc = t.flows[2].data->coll->mb();
-  launch_gemm_bf16(a.m, a.n, a.k, t.dev_ptr[0], a.ld, t.dev_ptr[1], a.ld,
-                   (float*)t.dev_ptr[2], ldc, g.stream, (int)a.j0);
+  launch_gemm_bf16(a.m, a.n, a.k, t.dev_ptr[0], a.ld, t.dev_ptr[1], (int)a.i0,
+                   (float*)t.dev_ptr[2], ldc, g.stream, (int)a.j0,
+                   a.seed & GB_A_MMAJOR, a.seed & GB_B_NMAJOR);
 }
 
 TaskClass& tc_fill_bf16() {
@@ -636,25 +645,33 @@ void insert_fill_bf16(Dtd& tp, TiledMatrix& A, uint32_t seed) {
     }
 }
 
-// C (fp32 mb x nb tiles) += At^T B over the shared K tiling. At: K x M
-// bf16 tiles (kb x mb each); B: K x N bf16 tiles (kb x nb).
-void insert_gemm_bf16(Dtd& tp, TiledMatrix& At, TiledMatrix& B,
-                      TiledMatrix& C) {
-  PA_CHECK(At.elem_size() == 2 && B.elem_size() == 2 && C.elem_size() == 4);
-  PA_CHECK(At.mt() == B.mt(), "K tilings must match");
-  PA_CHECK(At.nt() == C.mt() && B.nt() == C.nt());
-  const int KT = At.mt();
+// C (fp32 mb x nb tiles) = op(A) op(B) over the shared K tiling, every
+// matrix in column-major tiles. transa "T": A is K x M (kb x mb tiles, the
+// operand handed over transposed), "N": A is M x K (mb x kb tiles). transb
+// "N": B is K x N (kb x nb tiles), "T": B is N x K (nb x kb tiles).
+void insert_gemm_bf16(Dtd& tp, TiledMatrix& A, TiledMatrix& B, TiledMatrix& C,
+                      const std::string& transa, const std::string& transb) {
+  PA_CHECK(transa == "T" || transa == "N", "transa is \"T\" or \"N\"");
+  PA_CHECK(transb == "T" || transb == "N", "transb is \"T\" or \"N\"");
+  const bool am = transa == "N", bn = transb == "T";
+  PA_CHECK(A.elem_size() == 2 && B.elem_size() == 2 && C.elem_size() == 4);
+  const int KT = am ? A.nt() : A.mt();
+  PA_CHECK(KT == (bn ? B.nt() : B.mt()), "K tilings must match");
+  PA_CHECK((am ? A.mt() : A.nt()) == C.mt() &&
+           (bn ? B.mt() : B.nt()) == C.nt());
   for (int m = 0; m < C.mt(); m++)
     for (int n = 0; n < C.nt(); n++)
       for (int k = 0; k < KT; k++) {
         TileArgs a;
-        a.m = At.tile_cols(m);
-        a.n = B.tile_cols(n);
-        a.k = At.tile_rows(k);
-        a.ld = At.mb();
+        a.m = am ? A.tile_rows(m) : A.tile_cols(m);
+        a.n = bn ? B.tile_rows(n) : B.tile_cols(n);
+        a.k = am ? A.tile_cols(k) : A.tile_rows(k);
+        a.ld = A.mb();
+        a.i0 = B.mb();
         a.j0 = (k != 0);  // accumulate flag; k==0 overwrites C
-        Dtd::FlowSpec f[] = {{At.tile(k, m), ACCESS_IN},
-                             {B.tile(k, n), ACCESS_IN},
+        a.seed = (am ? GB_A_MMAJOR : 0) | (bn ? GB_B_NMAJOR : 0);
+        Dtd::FlowSpec f[] = {{am ? A.tile(m, k) : A.tile(k, m), ACCESS_IN},
+                             {bn ? B.tile(n, k) : B.tile(k, n), ACCESS_IN},
                              {C.tile(m, n),
                               k == 0 ? ACCESS_OUT : ACCESS_INOUT}};
         tp.insert(&tc_gemm_bf16(), &a, sizeof(a), f, 3, -(k),
@@ -663,7 +680,8 @@ void insert_gemm_bf16(Dtd& tp, TiledMatrix& At, TiledMatrix& B,
 }
 
 // kernel-level microbench (TFLOP/s)
-double bench_gemm_bf16(int m, int n, int k, int iters) {
+double bench_gemm_bf16(int m, int n, int k, int iters, bool a_mmajor,
+                       bool b_nmajor) {
   DevArray<bf16> dA((size_t)m * k), dB((size_t)n * k);
   DevArray<float> dC((size_t)m * n);
   hipLaunchKernelGGL(k_fill_bf16, dim3(2048), dim3(256), 0, 0, dA.p,
@@ -672,18 +690,24 @@ double bench_gemm_bf16(int m, int n, int k, int iters) {
                      (size_t)n * k, 2u);
   PA_HIP_CHECK(hipMemset(dC.p, 0, dC.bytes));
   double dt = time_launches(iters, [&] {
-    launch_gemm_bf16(m, n, k, dA.p, k, dB.p, k, dC.p, m, 0, 1);
+    launch_gemm_bf16(m, n, k, dA.p, a_mmajor ? m : k, dB.p, b_nmajor ? n : k,
+                     dC.p, m, 0, 1, a_mmajor, b_nmajor);
   });
   return 2.0 * m * n * k * iters / dt / 1e12;
 }
 
-// host-I/O numerics harness
+// host-I/O numerics harness: A holds lda x (k or m) elements, B ldb x (k or
+// n), C m x n; a leading dimension of 0 means the tight one.
 void test_gemm_bf16_hip(int m, int n, int k, const uint16_t* A,
-                        const uint16_t* B, float* C) {
-  DevArray<bf16> dA((size_t)m * k, (const bf16*)A),
-      dB((size_t)n * k, (const bf16*)B);
+                        const uint16_t* B, float* C, bool a_mmajor,
+                        bool b_nmajor, int lda, int ldb, int accum) {
+  if (!lda) lda = a_mmajor ? m : k;
+  if (!ldb) ldb = b_nmajor ? n : k;
+  DevArray<bf16> dA((size_t)lda * (a_mmajor ? k : m), (const bf16*)A),
+      dB((size_t)ldb * (b_nmajor ? k : n), (const bf16*)B);
   DevArray<float> dC((size_t)m * n, C);
-  launch_gemm_bf16(m, n, k, dA.p, k, dB.p, k, dC.p, m, 0, 1);
+  launch_gemm_bf16(m, n, k, dA.p, lda, dB.p, ldb, dC.p, m, 0, accum, a_mmajor,
+                   b_nmajor);
   dC.download(C);
 }
 

@@ -485,15 +485,53 @@ PYBIND11_MODULE(_core, m) {
         py::arg("A"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_fill_bf16", &insert_fill_bf16, py::arg("tp"), py::arg("A"),
         py::arg("seed") = 1u, py::call_guard<py::gil_scoped_release>());
-  m.def("insert_gemm_bf16", &insert_gemm_bf16, py::arg("tp"), py::arg("At"),
-        py::arg("B"), py::arg("C"), py::call_guard<py::gil_scoped_release>());
-  m.def("bench_gemm_bf16", [](int m, int n, int k, int iters) {
-    return pa::bench_gemm_bf16(m, n, k, iters);
-  }, py::call_guard<py::gil_scoped_release>());
+  m.def("insert_gemm_bf16", &insert_gemm_bf16, py::arg("tp"), py::arg("A"),
+        py::arg("B"), py::arg("C"), py::arg("transa") = "T",
+        py::arg("transb") = "N", py::call_guard<py::gil_scoped_release>());
+  // a bf16 GEMM operand layout letter ("T"/"N") as "stored M/N-major"
+  static auto bf16_major = [](const std::string& t, const char* major) {
+    if (t != "T" && t != "N")
+      throw std::invalid_argument("bf16 GEMM layout must be \"T\" or \"N\"");
+    return t == major;
+  };
+  m.def("bench_gemm_bf16", [](int m, int n, int k, int iters,
+                              const std::string& layout) {
+    if (layout.size() != 2)
+      throw std::invalid_argument("layout is one of TN, NN, NT, TT");
+    return pa::bench_gemm_bf16(m, n, k, iters,
+                               bf16_major(layout.substr(0, 1), "N"),
+                               bf16_major(layout.substr(1, 1), "T"));
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+        py::arg("layout") = "TN", py::call_guard<py::gil_scoped_release>());
+  // C (m x n, col-major) (+)= op(A) op(B) on host buffers. transa "T": A is
+  // k x m col-major, "N": m x k; transb "N": B is k x n col-major, "T":
+  // n x k. lda/ldb 0: the tight leading dimension of that layout.
   m.def("gemm_bf16_hip", [](py::array_t<uint16_t> A, py::array_t<uint16_t> B,
-                            py::array_t<float> C, int m, int n, int k) {
-    pa::test_gemm_bf16_hip(m, n, k, A.data(), B.data(), C.mutable_data());
-  });
+                            py::array_t<float> C, int m, int n, int k,
+                            const std::string& transa,
+                            const std::string& transb, int lda, int ldb,
+                            bool accum) {
+    const bool am = bf16_major(transa, "N"), bn = bf16_major(transb, "T");
+    if (m < 1 || n < 1 || k < 1)
+      throw std::invalid_argument("gemm_bf16_hip: m, n, k must be positive");
+    const int ra = am ? m : k, rb = bn ? n : k;  // stored rows
+    if (!lda) lda = ra;
+    if (!ldb) ldb = rb;
+    if (lda < ra || ldb < rb)
+      throw std::invalid_argument("gemm_bf16_hip: leading dimension too small");
+    // the TN kernels' dispatch looks at m, n, k alone: tight operands only
+    if (!am && !bn && (lda != k || ldb != k))
+      throw std::invalid_argument(
+          "gemm_bf16_hip: the TN layout takes tight leading dimensions");
+    if ((size_t)A.size() < (size_t)lda * (am ? k : m) ||
+        (size_t)B.size() < (size_t)ldb * (bn ? k : n) ||
+        (size_t)C.size() < (size_t)m * n)
+      throw std::invalid_argument("gemm_bf16_hip: buffer smaller than its shape");
+    pa::test_gemm_bf16_hip(m, n, k, A.data(), B.data(), C.mutable_data(), am,
+                           bn, lda, ldb, accum);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("transa") = "T", py::arg("transb") = "N",
+        py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("accum") = true);
 
   // PINS callback chain (mca/pins analog). Python callbacks fire from
   // worker threads: the wrapper takes the GIL. Returns a handle for
