@@ -63,6 +63,13 @@ struct TrsmSolveArgs {
   int unit = 0;   // unit diagonal (LU's L)
 };
 
+// Arguments of tc_gemm_fp8: C (fp32) = alpha A B^T (+ C when accum), both
+// operands K-major bytes. fmt_a/fmt_b: 0 = E4M3 (OCP e4m3fn), 1 = E5M2.
+struct GemmFp8Args {
+  int m, n, k, lda, ldb, accum, fmt_a, fmt_b;
+  float alpha;
+};
+
 // Every task-class id of the process in one place: the id is the key of the
 // trace header's class dictionary (profiling.cpp) and the row of the PINS
 // per-class counters (pins_modules.cpp), so two classes must never share
@@ -76,6 +83,8 @@ enum TaskClassId : int {
   TC_GEQRT = 10, TC_UNMQR = 11, TC_TSQRT = 12, TC_TSMQR = 13,
   // kernels_bf16.cpp
   TC_FILL_BF16 = 20, TC_GEMM_BF16 = 21,
+  // kernels_fp8.cpp
+  TC_FILL_FP8 = 22, TC_GEMM_FP8 = 23,
   // kernels_panel.cpp
   TC_PANEL_FILL = 24, TC_PANEL_FACTOR = 25, TC_PANEL_UPDATE = 26,
   // kernels_collections.cpp
@@ -143,6 +152,14 @@ void insert_fill_bf16(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_gemm_bf16(Dtd& tp, TiledMatrix& A, TiledMatrix& B, TiledMatrix& C,
                       const std::string& transa = "T",
                       const std::string& transb = "N");
+// Synthetic finite fp8 bytes, |x| < 2 in either format (kernels_fp8.cpp).
+void insert_fill_fp8(Dtd& tp, TiledMatrix& A, uint32_t seed);
+// C = alpha A^T B, OCP fp8 in ("e4m3" or "e5m2" per operand), fp32 out: A is
+// K x M in kb x mb tiles, B is K x N in kb x nb tiles, one byte per element
+// (kernels_fp8.cpp).
+void insert_gemm_fp8(Dtd& tp, TiledMatrix& A, TiledMatrix& B, TiledMatrix& C,
+                     const std::string& fmt_a = "e4m3",
+                     const std::string& fmt_b = "e4m3", float alpha = 1.0f);
 void insert_redistribute(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_reduce_axis(Dtd& tp, TiledMatrix& A, TiledMatrix& R, int axis);
 void insert_band_to_rect(Dtd& tp, TiledMatrix& S, TiledMatrix& D);

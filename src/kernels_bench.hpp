@@ -70,6 +70,15 @@ void test_gemm_bf16_hip(int m, int n, int k, const uint16_t* A,
                         bool b_nmajor = false, int lda = 0, int ldb = 0,
                         int accum = 1);
 
+// fp8 GEMM, C = alpha A B^T with K-major byte operands: TFLOP/s of the
+// kernel, and its host-memory test entry (kernels_fp8.cpp). fmt: 0 = E4M3,
+// 1 = E5M2; a leading dimension of 0 means k.
+double bench_gemm_fp8(int m, int n, int k, int iters, int fmt_a = 0,
+                      int fmt_b = 0);
+void test_gemm_fp8_hip(int m, int n, int k, const uint8_t* A, int fmt_a,
+                       const uint8_t* B, int fmt_b, float* C, float alpha = 1.f,
+                       int lda = 0, int ldb = 0, int accum = 0);
+
 // What bench_qr_factor times (kernels_qr.cpp); seconds for `iters`
 // factorizations of an m x k tile.
 enum QrBenchMode {

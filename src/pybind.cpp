@@ -533,6 +533,49 @@ PYBIND11_MODULE(_core, m) {
         py::arg("k"), py::arg("transa") = "T", py::arg("transb") = "N",
         py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("accum") = true);
 
+  m.def("insert_fill_fp8", &insert_fill_fp8, py::arg("tp"), py::arg("A"),
+        py::arg("seed") = 1u, py::call_guard<py::gil_scoped_release>());
+  m.def("insert_gemm_fp8", &insert_gemm_fp8, py::arg("tp"), py::arg("A"),
+        py::arg("B"), py::arg("C"), py::arg("fmt_a") = "e4m3",
+        py::arg("fmt_b") = "e4m3", py::arg("alpha") = 1.0f,
+        py::call_guard<py::gil_scoped_release>());
+  // an fp8 format name as the kernels' format number
+  static auto fp8_fmt = [](const std::string& f) {
+    if (f != "e4m3" && f != "e5m2")
+      throw std::invalid_argument("fp8 format must be \"e4m3\" or \"e5m2\"");
+    return (int)(f == "e5m2");
+  };
+  m.def("bench_gemm_fp8", [](int m, int n, int k, int iters,
+                             const std::string& fmt_a,
+                             const std::string& fmt_b) {
+    return pa::bench_gemm_fp8(m, n, k, iters, fp8_fmt(fmt_a), fp8_fmt(fmt_b));
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+        py::arg("fmt_a") = "e4m3", py::arg("fmt_b") = "e4m3",
+        py::call_guard<py::gil_scoped_release>());
+  // C (m x n, col-major) = alpha A B^T (+ C when accum) on host buffers: A
+  // is m rows of k fp8 bytes lda apart, B n rows of k bytes ldb apart
+  // (0: tight, k).
+  m.def("gemm_fp8_hip", [](py::array_t<uint8_t> A, py::array_t<uint8_t> B,
+                           py::array_t<float> C, int m, int n, int k,
+                           const std::string& fmt_a, const std::string& fmt_b,
+                           float alpha, int lda, int ldb, bool accum) {
+    const int fa = fp8_fmt(fmt_a), fb = fp8_fmt(fmt_b);
+    if (m < 1 || n < 1 || k < 1)
+      throw std::invalid_argument("gemm_fp8_hip: m, n, k must be positive");
+    if (!lda) lda = k;
+    if (!ldb) ldb = k;
+    if (lda < k || ldb < k)
+      throw std::invalid_argument("gemm_fp8_hip: leading dimension too small");
+    if ((size_t)A.size() < (size_t)lda * m || (size_t)B.size() < (size_t)ldb * n ||
+        (size_t)C.size() < (size_t)m * n)
+      throw std::invalid_argument("gemm_fp8_hip: buffer smaller than its shape");
+    pa::test_gemm_fp8_hip(m, n, k, A.data(), fa, B.data(), fb,
+                          C.mutable_data(), alpha, lda, ldb, accum);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("fmt_a") = "e4m3", py::arg("fmt_b") = "e4m3",
+        py::arg("alpha") = 1.0f, py::arg("lda") = 0, py::arg("ldb") = 0,
+        py::arg("accum") = false);
+
   // PINS callback chain (mca/pins analog). Python callbacks fire from
   // worker threads: the wrapper takes the GIL. Returns a handle for
   // pins_remove. events: list of names from PINS_EVENTS.
