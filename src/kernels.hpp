@@ -70,6 +70,20 @@ struct GemmFp8Args {
   float alpha;
 };
 
+// Arguments of tc_gemm_mxfp8: GemmFp8Args and the leading dimensions of the
+// E8M0 scale bytes, one per row and 32 K elements (kernels_mxfp8.cpp).
+struct GemmMxfp8Args {
+  int m, n, k, lda, ldb, accum, fmt_a, fmt_b;
+  float alpha;
+  int ldsa, ldsb;
+};
+
+// Arguments of tc_quant_mxfp8: X (fp32, rows x k, ldx) -> Q (bytes, ldq) and
+// S (ceil(k/32) scale bytes per row, lds). fmt as above.
+struct QuantMxfp8Args {
+  int rows, k, ldx, ldq, lds, fmt;
+};
+
 // Every task-class id of the process in one place: the id is the key of the
 // trace header's class dictionary (profiling.cpp) and the row of the PINS
 // per-class counters (pins_modules.cpp), so two classes must never share
@@ -85,6 +99,8 @@ enum TaskClassId : int {
   TC_FILL_BF16 = 20, TC_GEMM_BF16 = 21,
   // kernels_fp8.cpp
   TC_FILL_FP8 = 22, TC_GEMM_FP8 = 23,
+  // kernels_mxfp8.cpp
+  TC_GEMM_MXFP8 = 27, TC_QUANT_MXFP8 = 28, TC_FILL_F32 = 29,
   // kernels_panel.cpp
   TC_PANEL_FILL = 24, TC_PANEL_FACTOR = 25, TC_PANEL_UPDATE = 26,
   // kernels_collections.cpp
@@ -160,6 +176,23 @@ void insert_fill_fp8(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_gemm_fp8(Dtd& tp, TiledMatrix& A, TiledMatrix& B, TiledMatrix& C,
                      const std::string& fmt_a = "e4m3",
                      const std::string& fmt_b = "e4m3", float alpha = 1.0f);
+// C = alpha A^T B over MXFP8 operands: A, B, C as in insert_gemm_fp8, SA / SB
+// the E8M0 scale bytes (byte e is 2^(e-127), 255 NaN) of A / B, one per
+// column and 32 K elements: K/32 rows in tiles of A.mb()/32 rows and A's
+// column tiling, so tile (k, m) of SA scales tile (k, m) of A
+// (kernels_mxfp8.cpp).
+void insert_gemm_mxfp8(Dtd& tp, TiledMatrix& A, TiledMatrix& SA,
+                       TiledMatrix& B, TiledMatrix& SB, TiledMatrix& C,
+                       const std::string& fmt_a = "e4m3",
+                       const std::string& fmt_b = "e4m3", float alpha = 1.0f);
+// Synthetic fp32 values, integers in [-95, 96]: input for the quantiser
+// (kernels_mxfp8.cpp).
+void insert_fill_f32(Dtd& tp, TiledMatrix& A, uint32_t seed);
+// Quantise X (fp32, K x rows) to MXFP8 along K: Q its bytes in X's tiling, S
+// the scales tiled as above. Per block of 32: scale 2^(floor(log2 amax) -
+// emax), elements clamped to the finite range, rounded to nearest even.
+void insert_quantize_mxfp8(Dtd& tp, TiledMatrix& X, TiledMatrix& Q,
+                           TiledMatrix& S, const std::string& fmt = "e4m3");
 void insert_redistribute(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_reduce_axis(Dtd& tp, TiledMatrix& A, TiledMatrix& R, int axis);
 void insert_band_to_rect(Dtd& tp, TiledMatrix& S, TiledMatrix& D);

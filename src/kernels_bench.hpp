@@ -79,6 +79,21 @@ void test_gemm_fp8_hip(int m, int n, int k, const uint8_t* A, int fmt_a,
                        const uint8_t* B, int fmt_b, float* C, float alpha = 1.f,
                        int lda = 0, int ldb = 0, int accum = 0);
 
+// MXFP8 GEMM and quantiser (kernels_mxfp8.cpp): TFLOP/s of the GEMM kernel
+// on synthetic operands with scale bytes in 120..134, GB/s of the quantiser
+// over the bytes it reads and writes, and the host-memory test entries. SA /
+// SB hold ceil(k/32) scale bytes per row, ldsa / ldsb apart; the quantiser
+// writes Q (rows x k) and S (rows x ceil(k/32)) tight.
+double bench_gemm_mxfp8(int m, int n, int k, int iters, int fmt_a = 0,
+                        int fmt_b = 0);
+double bench_quantize_mxfp8(int rows, int k, int iters, int fmt = 0);
+void test_gemm_mxfp8_hip(int m, int n, int k, const uint8_t* A, int fmt_a,
+                         const uint8_t* SA, const uint8_t* B, int fmt_b,
+                         const uint8_t* SB, float* C, float alpha, int lda,
+                         int ldb, int ldsa, int ldsb, int accum);
+void test_quantize_mxfp8_hip(int rows, int k, int fmt, const float* X, int ldx,
+                             uint8_t* Q, uint8_t* S);
+
 // What bench_qr_factor times (kernels_qr.cpp); seconds for `iters`
 // factorizations of an m x k tile.
 enum QrBenchMode {

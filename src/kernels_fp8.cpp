@@ -12,8 +12,9 @@
 // MFMA consumes a 16 x 128-byte slab of each operand:
 //
 //   fragment   lane l holds row (l & 15), K bytes [(l >> 4) * 32, +32) of
-//              the step: 8 VGPRs, one 32-element MX block per lane (which is
-//              why the instruction takes one scale byte per lane).
+//              the step in 8 VGPRs. That is a permutation of the order the
+//              instruction numbers K in (kernels_fp8.hpp, f8_frag_mx), the
+//              same in A and B, so the product under unit scales is the same.
 //   result     lane l holds column (l & 15), rows (l >> 4) * 4 + 0..3, as
 //              every 16x16 MFMA.
 //
@@ -31,9 +32,10 @@
 // both reads of a fragment are conflict-free. Unswizzled, the 16 rows would
 // share two groups (an 8-way conflict).
 //
-// Out of scope here: MX block scales (the operand path is the one they need;
-// they replace the unit scale words), M/N-major operands, quantisation
-// kernels, FP6/FP4, bf16 output.
+// MX block scales (live scale registers on the same operand path) and the
+// fp32 -> MXFP8 quantiser are in kernels_mxfp8.cpp; what both files share is
+// in kernels_fp8.hpp. Out of scope here: M/N-major operands, FP6/FP4, bf16
+// output.
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -44,45 +46,10 @@
 #include "device_gpu.hpp"
 #include "kernels.hpp"
 #include "kernels_bench.hpp"
-#include "kernels_bf16.hpp"  // f32x4, bf_swz
+#include "kernels_fp8.hpp"
 #include "profiling.hpp"
 
 namespace pa {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
-#define F8_KS 128            // K bytes per step = LDS row stride
-#define F8_UNIT 0x7f7f7f7f   // E8M0 2^0 in every scale byte
-#define F8_BM 256            // fast kernel block
-#define F8_BN 256
-#define F8E_BM 128           // edge kernel block
-#define F8E_BN 128
-
-__device__ __forceinline__ int f8_key(int row) { return (row >> 1) & 7; }
-
-// The fragment of `row` for lane group g16 out of a swizzled step image.
-__device__ __forceinline__ i32x8 f8_frag(const char* img, int row, int g16) {
-  const char* p = img + row * F8_KS;
-  const int key = f8_key(row);
-  i32x4 lo = *(const i32x4*)(p + (((2 * g16) ^ key) << 4));
-  i32x4 hi = *(const i32x4*)(p + (((2 * g16 + 1) ^ key) << 4));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// FA/FB: 0 = E4M3, 1 = E5M2 (the cbsz / blgp encodings).
-template <int FA, int FB>
-__device__ __forceinline__ f32x4 f8_mfma(i32x8 a, i32x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-      a, b, c, FA, FB, 0, F8_UNIT, 0, F8_UNIT);
-}
-
-// An accumulator's MFMA chain up to here stays above this point: the
-// results are used only in the epilogue, and the compiler otherwise sinks
-// the MFMAs of the last K steps into it, with their fragments spilled.
-__device__ __forceinline__ void f8_pin(f32x4& v) {
-  asm volatile("" : "+v"(v));
-}
 
 // ------------------------------------------------------------ fast kernel
 // 256x256 block, 8 waves as 2(M) x 4(N), 128x64 per wave: 8x4 f32x4
@@ -241,22 +208,6 @@ __global__ void k_gemm_fp8(int m, int n, int k, const uint8_t* __restrict__ A,
 // through registers with guarded loads. Rows past m / n and bytes past k are
 // zero bytes, which is +0 in both formats, so the padding adds exact zeros.
 
-// 16 bytes of a row at K offset k0, zero past k; nothing is read when !ok.
-__device__ __forceinline__ i32x4 f8_load16(const uint8_t* row, bool ok, int k0,
-                                           int k) {
-  i32x4 v = {};
-  if (ok && k0 + 16 <= k) {
-    __builtin_memcpy(&v, row + k0, 16);
-  } else if (ok) {
-    unsigned w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int e = 0; e < 16; e++)
-      if (k0 + e < k) w[e >> 2] |= (unsigned)row[k0 + e] << (8 * (e & 3));
-    v = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-  }
-  return v;
-}
-
 template <int FA, int FB>
 __launch_bounds__(256)
 __global__ void k_gemm_fp8_edge(int m, int n, int k,
@@ -385,18 +336,6 @@ static void launch_gemm_fp8(int m, int n, int k, const void* A, int lda,
 }
 
 // -------------------------------------------------------------------- fill
-// A hashed byte with the top exponent bit cleared: the exponent field stays
-// below its all-ones value in either format, so no code is a NaN or an inf
-// and |x| < 2.
-__host__ __device__ static inline uint8_t fp8_fill_byte(size_t i,
-                                                        uint32_t seed) {
-  uint64_t h = (i * 2654435761ull) ^ ((uint64_t)seed * 2246822519ull);
-  h ^= h >> 13;
-  h *= 0x9E3779B97F4A7C15ull;
-  h ^= h >> 32;
-  return (uint8_t)(h & 0xBF);
-}
-
 // four bytes per store; nbytes is rounded down to a word, the tail bytewise
 __global__ void k_fill_fp8(uint8_t* p, size_t nbytes, uint32_t seed) {
   const size_t nw = nbytes / 4;
@@ -427,25 +366,6 @@ static void gpu_fill_fp8(Task& t, GpuTaskCtx& g) {
 }
 
 // ------------------------------------------------------------------ chores
-// The value of every byte code: [0] E4M3 (e4m3fn: S.1111.111 is NaN, there
-// is no inf), [1] E5M2 (IEEE-like: exponent 31 is inf / NaN).
-struct Fp8Tables {
-  float v[2][256];
-  Fp8Tables() {
-    for (int b = 0; b < 256; b++) {
-      const float s = b & 0x80 ? -1.f : 1.f;
-      int e = (b >> 3) & 15, f = b & 7;
-      v[0][b] = e == 15 && f == 7 ? NAN
-                : e == 0          ? s * std::ldexp((float)f, -9)
-                                  : s * std::ldexp(8.f + f, e - 10);
-      e = (b >> 2) & 31, f = b & 3;
-      v[1][b] = e == 31  ? (f ? NAN : s * INFINITY)
-                : e == 0 ? s * std::ldexp((float)f, -16)
-                         : s * std::ldexp(4.f + f, e - 17);
-    }
-  }
-};
-
 static void cpu_gemm_fp8(Task& t) {
   static const Fp8Tables tab;
   const GemmFp8Args& a = t.arg<GemmFp8Args>();
@@ -496,11 +416,6 @@ void insert_fill_fp8(Dtd& tp, TiledMatrix& A, uint32_t seed) {
       Dtd::FlowSpec f[] = {{A.tile(tm, tn), ACCESS_OUT}};
       tp.insert(&tc_fill_fp8(), &a, sizeof(a), f, 1, 0, A.rank_of(tm, tn));
     }
-}
-
-static int fp8_format(const std::string& f) {
-  PA_CHECK(f == "e4m3" || f == "e5m2", "fp8 format is \"e4m3\" or \"e5m2\"");
-  return f == "e5m2";
 }
 
 // The K chain of C(m, n) runs k = 0 (overwrite), 1, 2, ... (accumulate),

@@ -576,6 +576,83 @@ PYBIND11_MODULE(_core, m) {
         py::arg("alpha") = 1.0f, py::arg("lda") = 0, py::arg("ldb") = 0,
         py::arg("accum") = false);
 
+  m.def("insert_gemm_mxfp8", &insert_gemm_mxfp8, py::arg("tp"), py::arg("A"),
+        py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("fmt_a") = "e4m3", py::arg("fmt_b") = "e4m3",
+        py::arg("alpha") = 1.0f, py::call_guard<py::gil_scoped_release>());
+  m.def("insert_fill_f32", &insert_fill_f32, py::arg("tp"), py::arg("A"),
+        py::arg("seed") = 1u, py::call_guard<py::gil_scoped_release>());
+  m.def("insert_quantize_mxfp8", &insert_quantize_mxfp8, py::arg("tp"),
+        py::arg("X"), py::arg("Q"), py::arg("S"), py::arg("fmt") = "e4m3",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_gemm_mxfp8", [](int m, int n, int k, int iters,
+                               const std::string& fmt_a,
+                               const std::string& fmt_b) {
+    return pa::bench_gemm_mxfp8(m, n, k, iters, fp8_fmt(fmt_a),
+                                fp8_fmt(fmt_b));
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+        py::arg("fmt_a") = "e4m3", py::arg("fmt_b") = "e4m3",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_quantize_mxfp8", [](int rows, int k, int iters,
+                                   const std::string& fmt) {
+    return pa::bench_quantize_mxfp8(rows, k, iters, fp8_fmt(fmt));
+  }, py::arg("rows"), py::arg("k"), py::arg("iters"), py::arg("fmt") = "e4m3",
+        py::call_guard<py::gil_scoped_release>());
+  // gemm_fp8_hip with E8M0 block scales: SA is m rows of ceil(k/32) bytes
+  // ldsa apart, SB n rows ldsb apart (0: tight).
+  m.def("gemm_mxfp8_hip", [](py::array_t<uint8_t> A, py::array_t<uint8_t> SA,
+                             py::array_t<uint8_t> B, py::array_t<uint8_t> SB,
+                             py::array_t<float> C, int m, int n, int k,
+                             const std::string& fmt_a,
+                             const std::string& fmt_b, float alpha, int lda,
+                             int ldb, int ldsa, int ldsb, bool accum) {
+    const int fa = fp8_fmt(fmt_a), fb = fp8_fmt(fmt_b);
+    if (m < 1 || n < 1 || k < 1)
+      throw std::invalid_argument("gemm_mxfp8_hip: m, n, k must be positive");
+    const int kb = (k + 31) / 32;
+    if (!lda) lda = k;
+    if (!ldb) ldb = k;
+    if (!ldsa) ldsa = kb;
+    if (!ldsb) ldsb = kb;
+    if (lda < k || ldb < k || ldsa < kb || ldsb < kb)
+      throw std::invalid_argument(
+          "gemm_mxfp8_hip: leading dimension too small");
+    if ((size_t)A.size() < (size_t)lda * m ||
+        (size_t)B.size() < (size_t)ldb * n ||
+        (size_t)SA.size() < (size_t)ldsa * m ||
+        (size_t)SB.size() < (size_t)ldsb * n ||
+        (size_t)C.size() < (size_t)m * n)
+      throw std::invalid_argument(
+          "gemm_mxfp8_hip: buffer smaller than its shape");
+    pa::test_gemm_mxfp8_hip(m, n, k, A.data(), fa, SA.data(), B.data(), fb,
+                            SB.data(), C.mutable_data(), alpha, lda, ldb, ldsa,
+                            ldsb, accum);
+  }, py::arg("A"), py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("fmt_a") = "e4m3",
+        py::arg("fmt_b") = "e4m3", py::arg("alpha") = 1.0f,
+        py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldsa") = 0,
+        py::arg("ldsb") = 0, py::arg("accum") = false);
+  // X (rows of k floats ldx apart, 0: tight) -> (Q rows x k bytes, S rows x
+  // ceil(k/32) scale bytes), both tight.
+  m.def("quantize_mxfp8_hip", [](py::array_t<float> X, int rows, int k,
+                                 const std::string& fmt, int ldx) {
+    const int f = fp8_fmt(fmt);
+    if (rows < 1 || k < 1)
+      throw std::invalid_argument("quantize_mxfp8_hip: rows, k must be positive");
+    if (!ldx) ldx = k;
+    if (ldx < k)
+      throw std::invalid_argument(
+          "quantize_mxfp8_hip: leading dimension too small");
+    if ((size_t)X.size() < (size_t)ldx * rows)
+      throw std::invalid_argument(
+          "quantize_mxfp8_hip: buffer smaller than its shape");
+    py::array_t<uint8_t> Q({rows, k}), S({rows, (k + 31) / 32});
+    pa::test_quantize_mxfp8_hip(rows, k, f, X.data(), ldx, Q.mutable_data(),
+                                S.mutable_data());
+    return py::make_tuple(Q, S);
+  }, py::arg("X"), py::arg("rows"), py::arg("k"), py::arg("fmt") = "e4m3",
+        py::arg("ldx") = 0);
+
   // PINS callback chain (mca/pins analog). Python callbacks fire from
   // worker threads: the wrapper takes the GIL. Returns a handle for
   // pins_remove. events: list of names from PINS_EVENTS.
