@@ -84,6 +84,20 @@ struct QuantMxfp8Args {
   int rows, k, ldx, ldq, lds, fmt;
 };
 
+// Arguments of tc_gemm_mxfp4: k E2M1 elements per row, two to a byte; lda /
+// ldb in bytes, ldsa / ldsb as above (kernels_mxfp4.cpp).
+struct GemmMxfp4Args {
+  int m, n, k, lda, ldb, accum;
+  float alpha;
+  int ldsa, ldsb;
+};
+
+// Arguments of tc_quant_mxfp4: X (fp32, rows x k, ldx) -> Q (ceil(k/2) bytes
+// per row, ldq) and S (ceil(k/32) scale bytes per row, lds).
+struct QuantMxfp4Args {
+  int rows, k, ldx, ldq, lds;
+};
+
 // Every task-class id of the process in one place: the id is the key of the
 // trace header's class dictionary (profiling.cpp) and the row of the PINS
 // per-class counters (pins_modules.cpp), so two classes must never share
@@ -101,6 +115,8 @@ enum TaskClassId : int {
   TC_FILL_FP8 = 22, TC_GEMM_FP8 = 23,
   // kernels_mxfp8.cpp
   TC_GEMM_MXFP8 = 27, TC_QUANT_MXFP8 = 28, TC_FILL_F32 = 29,
+  // kernels_mxfp4.cpp
+  TC_GEMM_MXFP4 = 38, TC_QUANT_MXFP4 = 39,
   // kernels_panel.cpp
   TC_PANEL_FILL = 24, TC_PANEL_FACTOR = 25, TC_PANEL_UPDATE = 26,
   // kernels_collections.cpp
@@ -193,6 +209,18 @@ void insert_fill_f32(Dtd& tp, TiledMatrix& A, uint32_t seed);
 // emax), elements clamped to the finite range, rounded to nearest even.
 void insert_quantize_mxfp8(Dtd& tp, TiledMatrix& X, TiledMatrix& Q,
                            TiledMatrix& S, const std::string& fmt = "e4m3");
+// C = alpha A^T B over MXFP4 operands (E2M1, element 2q in the low nibble of
+// byte q): A is K/2 x M bytes in tiles of mb bytes (mb % 16 == 0, that is 32
+// elements) x columns, B likewise, SA / SB the E8M0 bytes, K/32 rows in
+// tiles of A.mb()/16 rows and A's column tiling (kernels_mxfp4.cpp).
+void insert_gemm_mxfp4(Dtd& tp, TiledMatrix& A, TiledMatrix& SA,
+                       TiledMatrix& B, TiledMatrix& SB, TiledMatrix& C,
+                       float alpha = 1.0f);
+// Quantise X (fp32, K x rows, K tile 2 * Q.mb()) to MXFP4 along K: Q the
+// packed elements, S the scales tiled as above. Per block of 32: scale
+// 2^(floor(log2 amax) - 2), elements clamped to +-6, rounded to nearest even.
+void insert_quantize_mxfp4(Dtd& tp, TiledMatrix& X, TiledMatrix& Q,
+                           TiledMatrix& S);
 void insert_redistribute(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_reduce_axis(Dtd& tp, TiledMatrix& A, TiledMatrix& R, int axis);
 void insert_band_to_rect(Dtd& tp, TiledMatrix& S, TiledMatrix& D);

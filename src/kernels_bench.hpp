@@ -94,6 +94,18 @@ void test_gemm_mxfp8_hip(int m, int n, int k, const uint8_t* A, int fmt_a,
 void test_quantize_mxfp8_hip(int rows, int k, int fmt, const float* X, int ldx,
                              uint8_t* Q, uint8_t* S);
 
+// MXFP4 GEMM and quantiser (kernels_mxfp4.cpp), as the MXFP8 entries above:
+// k counts E2M1 elements, two to a byte, lda / ldb are in bytes; the
+// quantiser writes Q (rows x ceil(k/2)) and S (rows x ceil(k/32)) tight.
+double bench_gemm_mxfp4(int m, int n, int k, int iters);
+double bench_quantize_mxfp4(int rows, int k, int iters);
+void test_gemm_mxfp4_hip(int m, int n, int k, const uint8_t* A,
+                         const uint8_t* SA, const uint8_t* B,
+                         const uint8_t* SB, float* C, float alpha, int lda,
+                         int ldb, int ldsa, int ldsb, int accum);
+void test_quantize_mxfp4_hip(int rows, int k, const float* X, int ldx,
+                             uint8_t* Q, uint8_t* S);
+
 // What bench_qr_factor times (kernels_qr.cpp); seconds for `iters`
 // factorizations of an m x k tile.
 enum QrBenchMode {

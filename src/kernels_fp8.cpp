@@ -34,8 +34,9 @@
 //
 // MX block scales (live scale registers on the same operand path) and the
 // fp32 -> MXFP8 quantiser are in kernels_mxfp8.cpp; what both files share is
-// in kernels_fp8.hpp. Out of scope here: M/N-major operands, FP6/FP4, bf16
-// output.
+// in kernels_fp8.hpp, and the same over packed FP4 (E2M1) elements is in
+// kernels_mxfp4.cpp. Out of scope here: M/N-major operands, FP6, mixed
+// FP8 x FP4 operand pairs, bf16 output.
 #include <atomic>
 #include <cmath>
 #include <cstring>

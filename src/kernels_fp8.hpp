@@ -1,5 +1,6 @@
 // What the fp8 kernel files share (kernels_fp8.cpp: unit block scales;
-// kernels_mxfp8.cpp: MX block scales and the quantiser): the step image and
+// kernels_mxfp8.cpp: MX block scales and the quantiser; kernels_mxfp4.cpp:
+// the same over packed E2M1 elements): the step image and
 // its swizzle, the fragment read, the scaled MFMA, the guarded 16-byte load,
 // the synthetic byte and the value tables of the CPU chores. The layout is
 // described at the head of kernels_fp8.cpp.
@@ -63,6 +64,37 @@ __device__ __forceinline__ f32x4 f8_mfma(i32x8 a, i32x8 b, f32x4 c,
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FA, FB, 0,
                                                           sa, 0, sb);
 }
+
+// FP4 (E2M1, two elements to a byte, element 2q in the low nibble of byte
+// q): the same instruction with cbsz = blgp = 4 takes four VGPRs per operand,
+// 32 K elements per lane, so f8_frag's eight VGPRs are two FP4 operands: half
+// H (0: the low four, chunk 2g of the row; 1: the high four, chunk 2g + 1)
+// is elements [64 g + 32 H, +32) of a 256-element step, its scale block
+// 2g + H. sa / sb hold the two E8M0 bytes of blocks 2g and 2g + 1 in bytes 0
+// and 1 and op_sel H picks the half's own. Measured on MI355X as
+// f8_frag_mx's layout was: here the ISA text holds as it stands.
+template <int H>
+__device__ __forceinline__ f32x4 f4_mfma(i32x8 a, i32x8 b, f32x4 c, int sa,
+                                         int sb) {
+  constexpr int o = 4 * H;
+  const i32x8 ah = __builtin_shufflevector(a, a, o, o + 1, o + 2, o + 3, -1,
+                                           -1, -1, -1);
+  const i32x8 bh = __builtin_shufflevector(b, b, o, o + 1, o + 2, o + 3, -1,
+                                           -1, -1, -1);
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ah, bh, c, 4, 4, H,
+                                                          sa, H, sb);
+}
+
+// The scale bytes of blocks 2g and 2g + 1 of `row` out of a scale image of
+// 8 bytes (one 256-element step) per row: one 16-bit read.
+__device__ __forceinline__ int f4_scale2(const char* simg, int row, int g16) {
+  return *(const uint16_t*)(simg + row * 8 + 2 * g16);
+}
+
+// The value of every E2M1 code s.ee.m; there is no NaN or inf code.
+inline constexpr float fp4_value[16] = {0.f,  0.5f,  1.f,  1.5f,  2.f,  3.f,
+                                        4.f,  6.f,   -0.f, -0.5f, -1.f, -1.5f,
+                                        -2.f, -3.f,  -4.f, -6.f};
 
 // An accumulator's MFMA chain up to here stays above this point: the
 // results are used only in the epilogue, and the compiler otherwise sinks

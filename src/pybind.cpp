@@ -653,6 +653,69 @@ PYBIND11_MODULE(_core, m) {
   }, py::arg("X"), py::arg("rows"), py::arg("k"), py::arg("fmt") = "e4m3",
         py::arg("ldx") = 0);
 
+  m.def("insert_gemm_mxfp4", &insert_gemm_mxfp4, py::arg("tp"), py::arg("A"),
+        py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("alpha") = 1.0f, py::call_guard<py::gil_scoped_release>());
+  m.def("insert_quantize_mxfp4", &insert_quantize_mxfp4, py::arg("tp"),
+        py::arg("X"), py::arg("Q"), py::arg("S"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_gemm_mxfp4", &pa::bench_gemm_mxfp4, py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("iters"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_quantize_mxfp4", &pa::bench_quantize_mxfp4, py::arg("rows"),
+        py::arg("k"), py::arg("iters"),
+        py::call_guard<py::gil_scoped_release>());
+  // gemm_mxfp8_hip over packed E2M1 rows: A is m rows of ceil(k/2) bytes lda
+  // apart (element 2q in the low nibble of byte q), B n rows ldb apart, the
+  // leading dimensions in bytes (0: tight).
+  m.def("gemm_mxfp4_hip", [](py::array_t<uint8_t> A, py::array_t<uint8_t> SA,
+                             py::array_t<uint8_t> B, py::array_t<uint8_t> SB,
+                             py::array_t<float> C, int m, int n, int k,
+                             float alpha, int lda, int ldb, int ldsa, int ldsb,
+                             bool accum) {
+    if (m < 1 || n < 1 || k < 1)
+      throw std::invalid_argument("gemm_mxfp4_hip: m, n, k must be positive");
+    const int kbytes = (k + 1) / 2, kb = (k + 31) / 32;
+    if (!lda) lda = kbytes;
+    if (!ldb) ldb = kbytes;
+    if (!ldsa) ldsa = kb;
+    if (!ldsb) ldsb = kb;
+    if (lda < kbytes || ldb < kbytes || ldsa < kb || ldsb < kb)
+      throw std::invalid_argument(
+          "gemm_mxfp4_hip: leading dimension too small");
+    if ((size_t)A.size() < (size_t)lda * m ||
+        (size_t)B.size() < (size_t)ldb * n ||
+        (size_t)SA.size() < (size_t)ldsa * m ||
+        (size_t)SB.size() < (size_t)ldsb * n ||
+        (size_t)C.size() < (size_t)m * n)
+      throw std::invalid_argument(
+          "gemm_mxfp4_hip: buffer smaller than its shape");
+    pa::test_gemm_mxfp4_hip(m, n, k, A.data(), SA.data(), B.data(), SB.data(),
+                            C.mutable_data(), alpha, lda, ldb, ldsa, ldsb,
+                            accum);
+  }, py::arg("A"), py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("alpha") = 1.0f,
+        py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldsa") = 0,
+        py::arg("ldsb") = 0, py::arg("accum") = false);
+  // X (rows of k floats ldx apart, 0: tight) -> (Q rows x ceil(k/2) bytes, S
+  // rows x ceil(k/32) scale bytes), both tight.
+  m.def("quantize_mxfp4_hip", [](py::array_t<float> X, int rows, int k,
+                                 int ldx) {
+    if (rows < 1 || k < 1)
+      throw std::invalid_argument("quantize_mxfp4_hip: rows, k must be positive");
+    if (!ldx) ldx = k;
+    if (ldx < k)
+      throw std::invalid_argument(
+          "quantize_mxfp4_hip: leading dimension too small");
+    if ((size_t)X.size() < (size_t)ldx * rows)
+      throw std::invalid_argument(
+          "quantize_mxfp4_hip: buffer smaller than its shape");
+    py::array_t<uint8_t> Q({rows, (k + 1) / 2}), S({rows, (k + 31) / 32});
+    pa::test_quantize_mxfp4_hip(rows, k, X.data(), ldx, Q.mutable_data(),
+                                S.mutable_data());
+    return py::make_tuple(Q, S);
+  }, py::arg("X"), py::arg("rows"), py::arg("k"), py::arg("ldx") = 0);
+
   // PINS callback chain (mca/pins analog). Python callbacks fire from
   // worker threads: the wrapper takes the GIL. Returns a handle for
   // pins_remove. events: list of names from PINS_EVENTS.
