@@ -98,6 +98,21 @@ struct QuantMxfp4Args {
   int rows, k, ldx, ldq, lds;
 };
 
+// Arguments of tc_gemm_mxfp6: k 6-bit elements per row, four to three bytes;
+// lda / ldb in bytes, ldsa / ldsb as above. fmt_a / fmt_b: 0 = E2M3, 1 = E3M2
+// (kernels_mxfp6.cpp).
+struct GemmMxfp6Args {
+  int m, n, k, lda, ldb, accum, fmt_a, fmt_b;
+  float alpha;
+  int ldsa, ldsb;
+};
+
+// Arguments of tc_quant_mxfp6: X (fp32, rows x k, ldx) -> Q (ceil(3k/4) bytes
+// per row, ldq) and S (ceil(k/32) scale bytes per row, lds). fmt as above.
+struct QuantMxfp6Args {
+  int rows, k, ldx, ldq, lds, fmt;
+};
+
 // Every task-class id of the process in one place: the id is the key of the
 // trace header's class dictionary (profiling.cpp) and the row of the PINS
 // per-class counters (pins_modules.cpp), so two classes must never share
@@ -117,6 +132,8 @@ enum TaskClassId : int {
   TC_GEMM_MXFP8 = 27, TC_QUANT_MXFP8 = 28, TC_FILL_F32 = 29,
   // kernels_mxfp4.cpp
   TC_GEMM_MXFP4 = 38, TC_QUANT_MXFP4 = 39,
+  // kernels_mxfp6.cpp
+  TC_GEMM_MXFP6 = 47, TC_QUANT_MXFP6 = 48,
   // kernels_panel.cpp
   TC_PANEL_FILL = 24, TC_PANEL_FACTOR = 25, TC_PANEL_UPDATE = 26,
   // kernels_collections.cpp
@@ -221,6 +238,22 @@ void insert_gemm_mxfp4(Dtd& tp, TiledMatrix& A, TiledMatrix& SA,
 // 2^(floor(log2 amax) - 2), elements clamped to +-6, rounded to nearest even.
 void insert_quantize_mxfp4(Dtd& tp, TiledMatrix& X, TiledMatrix& Q,
                            TiledMatrix& S);
+// C = alpha A^T B over MXFP6 operands (E2M3 or E3M2 per operand, element p in
+// bits [6p, 6p + 6) of the column): A is 3K/4 x M bytes in tiles of mb bytes
+// (mb % 24 == 0, that is 32 elements) x columns, B likewise, SA / SB the E8M0
+// bytes, K/32 rows in tiles of A.mb()/24 rows and A's column tiling; K is a
+// multiple of 4 (kernels_mxfp6.cpp).
+void insert_gemm_mxfp6(Dtd& tp, TiledMatrix& A, TiledMatrix& SA,
+                       TiledMatrix& B, TiledMatrix& SB, TiledMatrix& C,
+                       float alpha = 1.0f,
+                       const std::string& a_format = "e2m3",
+                       const std::string& b_format = "e2m3");
+// Quantise X (fp32, K x rows, K tile 4/3 Q.mb()) to MXFP6 along K: Q the
+// packed elements, S the scales tiled as above. Per block of 32: scale
+// 2^(floor(log2 amax) - emax), emax 2 (E2M3) or 4 (E3M2), elements clamped to
+// +-7.5 / +-28, rounded to nearest even.
+void insert_quantize_mxfp6(Dtd& tp, TiledMatrix& X, TiledMatrix& Q,
+                           TiledMatrix& S, const std::string& format = "e2m3");
 void insert_redistribute(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 void insert_reduce_axis(Dtd& tp, TiledMatrix& A, TiledMatrix& R, int axis);
 void insert_band_to_rect(Dtd& tp, TiledMatrix& S, TiledMatrix& D);

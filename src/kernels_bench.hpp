@@ -106,6 +106,19 @@ void test_gemm_mxfp4_hip(int m, int n, int k, const uint8_t* A,
 void test_quantize_mxfp4_hip(int rows, int k, const float* X, int ldx,
                              uint8_t* Q, uint8_t* S);
 
+// MXFP6 GEMM and quantiser (kernels_mxfp6.cpp), as the MXFP8 entries above:
+// k counts 6-bit elements, four to three bytes, lda / ldb are in bytes,
+// fmt 0 = E2M3, 1 = E3M2; the quantiser writes Q (rows x ceil(3k/4)) and S
+// (rows x ceil(k/32)) tight.
+double bench_gemm_mxfp6(int m, int n, int k, int iters, int fmt_a, int fmt_b);
+double bench_quantize_mxfp6(int rows, int k, int iters, int fmt);
+void test_gemm_mxfp6_hip(int m, int n, int k, const uint8_t* A, int fmt_a,
+                         const uint8_t* SA, const uint8_t* B, int fmt_b,
+                         const uint8_t* SB, float* C, float alpha, int lda,
+                         int ldb, int ldsa, int ldsb, int accum);
+void test_quantize_mxfp6_hip(int rows, int k, int fmt, const float* X, int ldx,
+                             uint8_t* Q, uint8_t* S);
+
 // What bench_qr_factor times (kernels_qr.cpp); seconds for `iters`
 // factorizations of an m x k tile.
 enum QrBenchMode {

@@ -716,6 +716,89 @@ PYBIND11_MODULE(_core, m) {
     return py::make_tuple(Q, S);
   }, py::arg("X"), py::arg("rows"), py::arg("k"), py::arg("ldx") = 0);
 
+  static auto fp6_fmt = [](const std::string& f) {
+    if (f != "e2m3" && f != "e3m2")
+      throw std::invalid_argument("fp6 format must be \"e2m3\" or \"e3m2\"");
+    return (int)(f == "e3m2");
+  };
+  m.def("insert_gemm_mxfp6", &insert_gemm_mxfp6, py::arg("tp"), py::arg("A"),
+        py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("alpha") = 1.0f, py::arg("a_format") = "e2m3",
+        py::arg("b_format") = "e2m3",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("insert_quantize_mxfp6", &insert_quantize_mxfp6, py::arg("tp"),
+        py::arg("X"), py::arg("Q"), py::arg("S"), py::arg("format") = "e2m3",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_gemm_mxfp6", [](int m, int n, int k, int iters,
+                               const std::string& a_format,
+                               const std::string& b_format) {
+    return pa::bench_gemm_mxfp6(m, n, k, iters, fp6_fmt(a_format),
+                                fp6_fmt(b_format));
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+        py::arg("a_format") = "e2m3", py::arg("b_format") = "e2m3",
+        py::call_guard<py::gil_scoped_release>());
+  m.def("bench_quantize_mxfp6", [](int rows, int k, int iters,
+                                   const std::string& format) {
+    return pa::bench_quantize_mxfp6(rows, k, iters, fp6_fmt(format));
+  }, py::arg("rows"), py::arg("k"), py::arg("iters"),
+        py::arg("format") = "e2m3", py::call_guard<py::gil_scoped_release>());
+  // gemm_mxfp4_hip over packed 6-bit rows: A is m rows of ceil(3k/4) bytes lda
+  // apart (element p in bits [6p, 6p + 6) of the row), B n rows ldb apart, the
+  // leading dimensions in bytes (0: tight).
+  m.def("gemm_mxfp6_hip", [](py::array_t<uint8_t> A, py::array_t<uint8_t> SA,
+                             py::array_t<uint8_t> B, py::array_t<uint8_t> SB,
+                             py::array_t<float> C, int m, int n, int k,
+                             const std::string& a_format,
+                             const std::string& b_format, float alpha, int lda,
+                             int ldb, int ldsa, int ldsb, bool accum) {
+    const int fa = fp6_fmt(a_format), fb = fp6_fmt(b_format);
+    if (m < 1 || n < 1 || k < 1)
+      throw std::invalid_argument("gemm_mxfp6_hip: m, n, k must be positive");
+    const int kbytes = (int)((3LL * k + 3) / 4), kb = (k + 31) / 32;
+    if (!lda) lda = kbytes;
+    if (!ldb) ldb = kbytes;
+    if (!ldsa) ldsa = kb;
+    if (!ldsb) ldsb = kb;
+    if (lda < kbytes || ldb < kbytes || ldsa < kb || ldsb < kb)
+      throw std::invalid_argument(
+          "gemm_mxfp6_hip: leading dimension too small");
+    if ((size_t)A.size() < (size_t)lda * m ||
+        (size_t)B.size() < (size_t)ldb * n ||
+        (size_t)SA.size() < (size_t)ldsa * m ||
+        (size_t)SB.size() < (size_t)ldsb * n ||
+        (size_t)C.size() < (size_t)m * n)
+      throw std::invalid_argument(
+          "gemm_mxfp6_hip: buffer smaller than its shape");
+    pa::test_gemm_mxfp6_hip(m, n, k, A.data(), fa, SA.data(), B.data(), fb,
+                            SB.data(), C.mutable_data(), alpha, lda, ldb, ldsa,
+                            ldsb, accum);
+  }, py::arg("A"), py::arg("SA"), py::arg("B"), py::arg("SB"), py::arg("C"),
+        py::arg("m"), py::arg("n"), py::arg("k"), py::arg("a_format") = "e2m3",
+        py::arg("b_format") = "e2m3", py::arg("alpha") = 1.0f,
+        py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldsa") = 0,
+        py::arg("ldsb") = 0, py::arg("accum") = false);
+  // X (rows of k floats ldx apart, 0: tight) -> (Q rows x ceil(3k/4) bytes, S
+  // rows x ceil(k/32) scale bytes), both tight.
+  m.def("quantize_mxfp6_hip", [](py::array_t<float> X, int rows, int k,
+                                 const std::string& format, int ldx) {
+    const int f = fp6_fmt(format);
+    if (rows < 1 || k < 1)
+      throw std::invalid_argument("quantize_mxfp6_hip: rows, k must be positive");
+    if (!ldx) ldx = k;
+    if (ldx < k)
+      throw std::invalid_argument(
+          "quantize_mxfp6_hip: leading dimension too small");
+    if ((size_t)X.size() < (size_t)ldx * rows)
+      throw std::invalid_argument(
+          "quantize_mxfp6_hip: buffer smaller than its shape");
+    py::array_t<uint8_t> Q({rows, (int)((3LL * k + 3) / 4)}),
+        S({rows, (k + 31) / 32});
+    pa::test_quantize_mxfp6_hip(rows, k, f, X.data(), ldx, Q.mutable_data(),
+                                S.mutable_data());
+    return py::make_tuple(Q, S);
+  }, py::arg("X"), py::arg("rows"), py::arg("k"), py::arg("format") = "e2m3",
+        py::arg("ldx") = 0);
+
   // PINS callback chain (mca/pins analog). Python callbacks fire from
   // worker threads: the wrapper takes the GIL. Returns a handle for
   // pins_remove. events: list of names from PINS_EVENTS.
