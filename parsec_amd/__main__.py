@@ -28,7 +28,7 @@ def main():
           "gpu_mem_percent, gpu_mem_limit_mb, chore_gemm (rocblas|hip), "
           "chore_syrk (hip|dgemm|syrkx), chore_potrf (hip|rocsolver), "
           "chore_potrf_syrk (hip|rocblas), chore_trsm_inv (hip|rocblas), "
-          "chore_qr (hand|rocsolver), qr_algo (house|bcgs), trsm_variant "
+          "dgemm_nt_kernel (3|4), chore_qr (hand|rocsolver), qr_algo (house|bcgs), trsm_variant "
           "(invgemm|rocblas), dtd_window_size, comm_kind (tcp|rccl), "
           "comm_max_inflight, comm_send_reserve, bcast_tree "
           "(unicast|binomial), comm_base_port, profile_filename, "

@@ -31,6 +31,14 @@
 //               TRSM-by-inverse product: each output block column's K loop
 //               stops at its diagonal block, where a dense dgemm spends half
 //               its flops on W's stored zeros (chore_trsm_inv=hip|rocblas)
+//  - k_dgemm_nt_v4<KIND, S, BK>, v3's three kinds on a K-pipelined body: an
+//    LDS ring of S slots, S - 1 K-tiles of copies in flight, a counted vmcnt
+//    wait and one raw barrier per K-tile where v3 drains every copy per
+//    K-tile. Same blocks, fragments and summation order, so the same bits.
+//    Instantiated with S = 3, BK = 16 (96 KB, one block per CU). It is the
+//    slower of the two alone and the faster inside the Cholesky DAG, beside
+//    the library GEMM's blocks (profiles/RESULTS.md), and is what the
+//    full-tile launches take: PARSEC_MCA_dgemm_nt_kernel=4 (default) | 3.
 //  - k_dgemm_nt_v2<TRI>, the bounds-checked kernel for every other GEMM and
 //    SYRK shape: register-staged, zero-filled past the edges.
 //  - k_dgemm_tn<KIND>, the bounds-checked kernel for C (+)= A^T B with
@@ -42,6 +50,7 @@
 //  - k_potf2_mfma, the in-LDS Cholesky of one <=128 diagonal block.
 #include "kernels_hip.hpp"
 
+#include "gpu_blas.hpp"
 #include "kernels.hpp"
 #include "kernels_bench.hpp"
 
@@ -52,6 +61,11 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 #define BM 128
 #define BN 128
 #define BKD 16
+// k_dgemm_nt_v4's ring: slots and K-rows per slot
+#define V4_S 3
+#define V4_BK 16
+// PARSEC_MCA_dgemm_nt_kernel when it is not set
+#define NT_KERNEL_DEFAULT 4
 
 // Both GEMM kernels run 8 waves as 4(M) x 2(N) on a 128x128 block, each
 // wave owning 32x64 as 2x4 MFMA fragments (64 accumulator VGPRs), with K
@@ -91,14 +105,15 @@ __device__ __forceinline__ void block_decode(bool tri, int nbx, int& bx,
   }
 }
 
-// One BKD-deep K-tile into the wave's 2x4 accumulators. ap / bp point at
+// One DEPTH-deep K-tile into the wave's 2x4 accumulators. ap / bp point at
 // this lane's element of the first A / B fragment in a [k][row] LDS image
 // whose K-rows are ld doubles apart.
+template <int DEPTH = BKD>
 __device__ __forceinline__ void mfma_ktile(f64x4 (&acc)[2][4],
                                            const double* ap, const double* bp,
                                            int ld) {
 #pragma unroll
-  for (int kk = 0; kk < BKD; kk += 4) {
+  for (int kk = 0; kk < DEPTH; kk += 4) {
     double a[2], b[4];
 #pragma unroll
     for (int f = 0; f < 2; f++) a[f] = ap[kk * ld + f * 16];
@@ -269,6 +284,108 @@ __global__ void k_dgemm_nt_v3(int m, int n, int k, const double* __restrict__ A,
           /*checked=*/false, /*store=*/KIND == V3_TRMM);
 }
 
+// ------------------------------------------------------------------ v4
+// v3 with the K loop's staging replaced by a ring: S LDS slots of BK K-rows,
+// the copies of D = S - 1 K-tiles in flight, a counted wait and one raw
+// barrier per K-tile. v3 drains every copy (vmcnt(0) inside __syncthreads)
+// once per K-tile, so its prefetch distance is the 32 MFMAs of one tile and
+// it leans on a second block of itself on the CU to cover the rest. Block
+// decode, fragment map, mfma_ktile, write_c and the ascending-k order are
+// v3's, so the two give the same bits. Measured (profiles/RESULTS.md): of
+// S = 3 BK = 16, S = 4 BK = 8 and S = 4 BK = 16 the first had the shortest
+// side-by-side mix time and is the one instantiated; alone every one of them
+// is slower than v3.
+//
+// Iteration t (slot t % S):
+//   s_waitcnt vmcnt(c)   this wave's copies of tile t have landed; c counts
+//                        the copies of the tiles after t that were issued,
+//                        CPS * (D - 1) in steady state and fewer over the
+//                        last D - 1 tiles, down to 0
+//   s_barrier            ... and so have every wave's; every wave is also
+//                        done reading slot (t - 1) % S
+//   issue tile t + D into slot (t + D) % S == (t - 1) % S, if t + D < ntiles
+//   the MFMAs of tile t
+// A wave that has passed barrier t + 1 may overwrite slot t % S only because
+// every wave reached that barrier after its reads of tile t (an MFMA waits
+// for its LDS operands, so the reads are complete, not merely issued). No
+// copy is ever issued for a tile >= ntiles, and the prologue issues
+// min(D, ntiles) tiles (the in-tile POTRF update has k = 128, the first TRMM
+// block column kend = 128).
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int KIND, int S, int BK>
+__launch_bounds__(512)
+__global__ void k_dgemm_nt_v4(int m, int n, int k, const double* __restrict__ A,
+                              int lda, const double* __restrict__ B, int ldb,
+                              double* __restrict__ C, int ldc, int nbx) {
+  static_assert(S == 3 || S == 4, "the drain below covers D = 2 and D = 3");
+  static_assert(BK == 8 || BK == 16, "one or two K-rows per wave and operand");
+  constexpr int D = S - 1;
+  constexpr int RPW = BK / 8;    // K-rows per wave, of A and of B
+  constexpr int CPS = 2 * RPW;   // copies per lane and stage
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* As = (double*)smem;                  // [S][BK][BM]
+  double* Bs = As + S * BK * BM;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  int bx, by;
+  if (KIND == V3_TRMM) {
+    const int nby = n / BN;
+    const int xcd = blockIdx.x & 7, pos = blockIdx.x >> 3;
+    const int round = pos / nbx;
+    const int rank = round * 8 + ((round & 1) ? 7 - xcd : xcd);
+    if (rank >= nby) return;  // padding block (whole block, before any barrier)
+    bx = pos - round * nbx;
+    by = nby - 1 - rank;
+  } else {
+    block_decode(KIND == V3_SYRK, nbx, bx, by);
+  }
+  const int bm0 = bx * BM, bn0 = by * BN;
+  const int ksub = lane >> 4, r16 = lane & 15;
+  const int kend = KIND == V3_TRMM ? (bn0 + BN < k ? bn0 + BN : k) : k;
+
+  f64x4 acc[2][4] = {};
+
+  auto stage = [&](int slot, int k0) {
+#pragma unroll
+    for (int p = 0; p < RPW; p++) {
+      int krow = wave * RPW + p;
+      const double* srcA = A + (size_t)(k0 + krow) * lda + bm0 + 2 * lane;
+      double* dstA = As + (slot * BK + krow) * BM;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)srcA,
+          (__attribute__((address_space(3))) unsigned int*)dstA, 16, 0, 0);
+      const double* srcB = B + (size_t)(k0 + krow) * ldb + bn0 + 2 * lane;
+      double* dstB = Bs + (slot * BK + krow) * BN;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) unsigned int*)srcB,
+          (__attribute__((address_space(3))) unsigned int*)dstB, 16, 0, 0);
+    }
+  };
+
+  const int ntiles = kend / BK;
+  for (int t = 0; t < D && t < ntiles; t++) stage(t, t * BK);
+  int rslot = 0, wslot = D;  // t % S and (t + D) % S
+  for (int t = 0; t < ntiles; t++) {
+    const int after = ntiles - 1 - t;  // tiles after t
+    if (after >= D - 1) wait_vmcnt<CPS * (D - 1)>();
+    else if (D == 3 && after == 1) wait_vmcnt<CPS>();
+    else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    if (t + D < ntiles) stage(wslot, (t + D) * BK);
+    mfma_ktile<BK>(acc, As + (rslot * BK + ksub) * BM + wr * 32 + r16,
+                   Bs + (rslot * BK + ksub) * BN + wc * 64 + r16, BM);
+    rslot = rslot + 1 == S ? 0 : rslot + 1;
+    wslot = wslot + 1 == S ? 0 : wslot + 1;
+  }
+  write_c(acc, C, ldc, bm0 + wr * 32 + ksub, bn0 + wc * 64 + r16, m, n,
+          /*checked=*/false, /*store=*/KIND == V3_TRMM);
+}
+
 // ------------------------------------------------------------------ tn
 // C[m x n] (+)= A[k x m]^T B[k x n]: both operands are contiguous along K,
 // the layout of the second half of the SPD inverse (A^-1 = W^T W with
@@ -420,49 +537,71 @@ static void launch_lds(int grid, int block, size_t lds, hipStream_t stream,
 
 constexpr size_t LDS_V2 = 4 * BKD * 129 * 8;
 constexpr size_t LDS_V3 = 2 * BKD * (BM + BN) * 8;
+constexpr size_t LDS_V4 = V4_S * V4_BK * (BM + BN) * 8;
 
-// What the glds kernel can take: whole 128-blocks, whole K-tiles, and, as
-// it stages 16 B per lane, operands whose every column starts 16-B aligned
+// What the glds kernels can take: whole 128-blocks, whole K-tiles, and, as
+// they stage 16 B per lane, operands whose every column starts 16-B aligned
 // (even leading dimension).
 static bool full_tiles(int m, int n, int k, int lda, int ldb) {
   return m % BM == 0 && n % BN == 0 && k % BKD == 0 && lda % 2 == 0 &&
          ldb % 2 == 0;
 }
 
+// Which full-tile kernel: `kernel` when a caller names one (the test and
+// bench entries), otherwise PARSEC_MCA_dgemm_nt_kernel, read once.
+static int nt_kernel(int kernel) {
+  static const int param = (int)param_int("dgemm_nt_kernel", NT_KERNEL_DEFAULT);
+  if (kernel == 0) kernel = param;
+  PA_CHECK(kernel == 3 || kernel == 4, "dgemm_nt_kernel is 3 or 4, got %d",
+           kernel);
+  return kernel;
+}
+
+// One full-tile launch of KIND on the chosen kernel.
+template <int KIND, typename... Args>
+static void launch_full(int kernel, int grid, hipStream_t stream,
+                        Args... args) {
+  if (nt_kernel(kernel) == 3)
+    launch_lds<k_dgemm_nt_v3<KIND>>(grid, 512, LDS_V3, stream, args...);
+  else
+    launch_lds<k_dgemm_nt_v4<KIND, V4_S, V4_BK>>(grid, 512, LDS_V4, stream,
+                                                 args...);
+}
+
 void launch_dgemm_nt(int m, int n, int k, const double* A, int lda,
                      const double* B, int ldb, double* C, int ldc,
-                     hipStream_t stream) {
+                     hipStream_t stream, int kernel) {
   const int nbx = (m + BM - 1) / BM, nby = (n + BN - 1) / BN;
   if (full_tiles(m, n, k, lda, ldb))
-    launch_lds<k_dgemm_nt_v3<V3_GEMM>>(nbx * nby, 512, LDS_V3, stream, m, n, k,
-                                       A, lda, B, ldb, C, ldc, nbx);
+    launch_full<V3_GEMM>(kernel, nbx * nby, stream, m, n, k, A, lda, B, ldb, C,
+                         ldc, nbx);
   else
     launch_lds<k_dgemm_nt_v2<false>>(nbx * nby, 512, LDS_V2, stream, m, n, k,
                                      A, lda, B, ldb, C, ldc, nbx);
 }
 
 void launch_dsyrk_ln(int n, int k, const double* A, int lda, double* C,
-                     int ldc, hipStream_t stream) {
+                     int ldc, hipStream_t stream, int kernel) {
   const int ntb = (n + BM - 1) / BM;
   const int nblocks = ntb * (ntb + 1) / 2;
   if (full_tiles(n, n, k, lda, lda))
-    launch_lds<k_dgemm_nt_v3<V3_SYRK>>(nblocks, 512, LDS_V3, stream, n, n, k,
-                                       A, lda, A, lda, C, ldc, 0);
+    launch_full<V3_SYRK>(kernel, nblocks, stream, n, n, k, A, lda, A, lda, C,
+                         ldc, 0);
   else
     launch_lds<k_dgemm_nt_v2<true>>(nblocks, 512, LDS_V2, stream, n, n, k, A,
                                     lda, A, lda, C, ldc, 0);
 }
 
 void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
-                      int ldw, double* X, int ldx, hipStream_t stream) {
+                      int ldw, double* X, int ldx, hipStream_t stream,
+                      int kernel) {
   PA_CHECK(m > 0 && n > 0 && full_tiles(m, n, n, ldb, ldw),
            "dtrmm_rlt needs full 128x128 blocks and even ld, got %d x %d, "
            "ldb %d, ldw %d", m, n, ldb, ldw);
   PA_CHECK(ldb >= m && ldx >= m && ldw >= n);
   const int nbx = m / BM, nby = n / BN;
-  launch_lds<k_dgemm_nt_v3<V3_TRMM>>(8 * ((nby + 7) / 8) * nbx, 512, LDS_V3,
-                                     stream, m, n, n, B, ldb, W, ldw, X, ldx,
-                                     nbx);
+  launch_full<V3_TRMM>(kernel, 8 * ((nby + 7) / 8) * nbx, stream, m, n, n, B,
+                       ldb, W, ldw, X, ldx, nbx);
 }
 
 void launch_dgemm_tn(int m, int n, int k, const double* A, int lda,
@@ -628,27 +767,29 @@ void bench_fill(DevArray<double>& a, uint32_t seed) {
 }  // namespace
 
 void test_dgemm_nt_hip(int m, int n, int k, const double* A, int lda,
-                       const double* B, int ldb, double* C, int ldc) {
+                       const double* B, int ldb, double* C, int ldc,
+                       int kernel) {
   DevArray dA((size_t)lda * k, A), dB((size_t)ldb * k, B),
       dC((size_t)ldc * n, C);
-  launch_dgemm_nt(m, n, k, dA.p, lda, dB.p, ldb, dC.p, ldc, 0);
+  launch_dgemm_nt(m, n, k, dA.p, lda, dB.p, ldb, dC.p, ldc, 0, kernel);
   dC.download(C);
 }
 
 void test_dsyrk_ln_hip(int n, int k, const double* A, int lda, double* C,
-                       int ldc) {
+                       int ldc, int kernel) {
   DevArray dA((size_t)lda * k, A), dC((size_t)ldc * n, C);
-  launch_dsyrk_ln(n, k, dA.p, lda, dC.p, ldc, 0);
+  launch_dsyrk_ln(n, k, dA.p, lda, dC.p, ldc, 0, kernel);
   dC.download(C);
 }
 
 // X is uploaded too, so a caller can show that whatever the output buffer
 // held is ignored (beta = 0).
 void test_dtrmm_rlt_hip(int m, int n, const double* B, int ldb,
-                        const double* W, int ldw, double* X, int ldx) {
+                        const double* W, int ldw, double* X, int ldx,
+                        int kernel) {
   DevArray dB((size_t)ldb * n, B), dW((size_t)ldw * n, W),
       dX((size_t)ldx * n, X);
-  launch_dtrmm_rlt(m, n, dB.p, ldb, dW.p, ldw, dX.p, ldx, 0);
+  launch_dtrmm_rlt(m, n, dB.p, ldb, dW.p, ldw, dX.p, ldx, 0, kernel);
   dX.download(X);
 }
 
@@ -697,13 +838,22 @@ void test_potf2_hip(double* A, int n) {
 }
 
 // The rocBLAS comparison lives in kernels_blas.cpp.
-double bench_dgemm_hip(int m, int n, int k, int iters) {
+double bench_dgemm_hip(int m, int n, int k, int iters, int kernel) {
   DevArray dA((size_t)m * k), dB((size_t)n * k), dC((size_t)m * n);
   bench_fill(dA, 11);
   bench_fill(dB, 12);
   bench_fill(dC, 13);
   return time_launches(iters, [&] {
-    launch_dgemm_nt(m, n, k, dA.p, m, dB.p, n, dC.p, m, 0);
+    launch_dgemm_nt(m, n, k, dA.p, m, dB.p, n, dC.p, m, 0, kernel);
+  });
+}
+
+double bench_dsyrk_hip(int n, int k, int iters, int kernel) {
+  DevArray dA((size_t)n * k), dC((size_t)n * n);
+  bench_fill(dA, 11);
+  bench_fill(dC, 13);
+  return time_launches(iters, [&] {
+    launch_dsyrk_ln(n, k, dA.p, n, dC.p, n, 0, kernel);
   });
 }
 
@@ -741,17 +891,99 @@ double bench_dgemm_nn_hip(int m, int n, int k, int iters) {
   });
 }
 
+// Zero the strictly-upper part of the n x n W.
+static __global__ void k_bench_zero_upper(double* W, int n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i < (size_t)n * n; i += (size_t)gridDim.x * blockDim.x)
+    if (i % n < i / n) W[i] = 0.0;
+}
+
 // W is lower triangular with zeros above.
-double bench_dtrmm_hip(int m, int n, int iters) {
+double bench_dtrmm_hip(int m, int n, int iters, int kernel) {
   DevArray dB((size_t)m * n), dW((size_t)n * n), dX((size_t)m * n);
   bench_fill(dB, 11);
   bench_fill(dW, 12);
-  // zero the strictly-upper part of W, column by column
-  for (int c = 1; c < n; c++)
-    PA_HIP_CHECK(hipMemsetAsync(dW.p + (size_t)c * n, 0, (size_t)c * 8, 0));
+  hipLaunchKernelGGL(k_bench_zero_upper, dim3(2048), dim3(256), 0, 0, dW.p, n);
   return time_launches(iters, [&] {
-    launch_dtrmm_rlt(m, n, dB.p, m, dW.p, n, dX.p, m, 0);
+    launch_dtrmm_rlt(m, n, dB.p, m, dW.p, n, dX.p, m, 0, kernel);
   });
+}
+
+CoresidentTimes bench_coresident(int nb, int per_round, int kernel) {
+  PA_CHECK(nb > 0 && nb % BM == 0 && per_round > 0 && per_round % 2 == 0,
+           "bench_coresident: nb a multiple of 128, per_round even, got %d %d",
+           nb, per_round);
+  const size_t tile = (size_t)nb * nb;
+  // every stream has operands and an output of its own
+  DevArray gA0(tile), gB0(tile), gC0(tile), gA1(tile), gB1(tile), gC1(tile);
+  DevArray sA(tile), sC(tile), tB(tile), tW(tile), tX(tile);
+  uint32_t seed = 11;
+  for (DevArray<double>* a :
+       {&gA0, &gB0, &gC0, &gA1, &gB1, &gC1, &sA, &sC, &tB, &tW})
+    bench_fill(*a, seed++);
+  hipLaunchKernelGGL(k_bench_zero_upper, dim3(2048), dim3(256), 0, 0, tW.p, nb);
+
+  enum { G0, G1, SY, TR, NS };
+  hipStream_t st[NS];
+  hipEvent_t beg[NS], end[NS];
+  rocblas_handle h[2];
+  for (int i = 0; i < NS; i++) {
+    PA_HIP_CHECK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
+    PA_HIP_CHECK(hipEventCreate(&beg[i]));
+    PA_HIP_CHECK(hipEventCreate(&end[i]));
+  }
+  for (int i = 0; i < 2; i++) {
+    PA_BLAS_CHECK(rocblas_create_handle(&h[i]));
+    PA_BLAS_CHECK(rocblas_set_stream(h[i], st[i]));
+  }
+  const double mone = -1.0, one = 1.0;
+  auto launch = [&](int i) {
+    switch (i) {
+      case G0:
+        PA_BLAS_CHECK(rocblas_dgemm(
+            h[0], rocblas_operation_none, rocblas_operation_transpose, nb, nb,
+            nb, &mone, gA0.p, nb, gB0.p, nb, &one, gC0.p, nb));
+        break;
+      case G1:
+        PA_BLAS_CHECK(rocblas_dgemm(
+            h[1], rocblas_operation_none, rocblas_operation_transpose, nb, nb,
+            nb, &mone, gA1.p, nb, gB1.p, nb, &one, gC1.p, nb));
+        break;
+      case SY: launch_dsyrk_ln(nb, nb, sA.p, nb, sC.p, nb, st[SY], kernel); break;
+      default:
+        launch_dtrmm_rlt(nb, nb, tB.p, nb, tW.p, nb, tX.p, nb, st[TR], kernel);
+    }
+  };
+  for (int i = 0; i < NS; i++) launch(i);
+  PA_HIP_CHECK(hipDeviceSynchronize());
+
+  const int count[NS] = {5 * per_round / 2, 5 * per_round / 2, per_round,
+                         per_round};
+  double t0 = now_s();
+  for (int i = 0; i < NS; i++) PA_HIP_CHECK(hipEventRecord(beg[i], st[i]));
+  // round-robin, so that no stream's queue runs dry while another's fills
+  for (int r = 0; r < count[G0]; r++)
+    for (int i = 0; i < NS; i++)
+      if (r < count[i]) launch(i);
+  for (int i = 0; i < NS; i++) PA_HIP_CHECK(hipEventRecord(end[i], st[i]));
+  for (int i = 0; i < NS; i++) PA_HIP_CHECK(hipStreamSynchronize(st[i]));
+  CoresidentTimes r;
+  r.wall_s = now_s() - t0;
+  float ms[NS];
+  for (int i = 0; i < NS; i++)
+    PA_HIP_CHECK(hipEventElapsedTime(&ms[i], beg[i], end[i]));
+  r.gemm_s[0] = ms[G0] * 1e-3;
+  r.gemm_s[1] = ms[G1] * 1e-3;
+  r.syrk_s = ms[SY] * 1e-3;
+  r.trmm_s = ms[TR] * 1e-3;
+  PA_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < 2; i++) rocblas_destroy_handle(h[i]);
+  for (int i = 0; i < NS; i++) {
+    PA_HIP_CHECK(hipEventDestroy(beg[i]));
+    PA_HIP_CHECK(hipEventDestroy(end[i]));
+    PA_HIP_CHECK(hipStreamDestroy(st[i]));
+  }
+  return r;
 }
 
 }  // namespace pa

@@ -7,19 +7,24 @@
 
 namespace pa {
 
+// The first three launchers send shapes of whole 128-blocks, k % 16 == 0 and
+// even leading dimensions to a full-tile kernel: `kernel` 3 is
+// k_dgemm_nt_v3, 4 is k_dgemm_nt_v4 (same bits), 0 takes
+// PARSEC_MCA_dgemm_nt_kernel. Other shapes ignore it.
 // C[m x n] -= A[m x k] * B[n x k]^T
 void launch_dgemm_nt(int m, int n, int k, const double* A, int lda,
                      const double* B, int ldb, double* C, int ldc,
-                     hipStream_t stream);
+                     hipStream_t stream, int kernel = 0);
 // C[n x n] -= A[n x k] * A^T on the lower-triangular set of 128-blocks
 // (diagonal blocks are computed whole)
 void launch_dsyrk_ln(int n, int k, const double* A, int lda, double* C,
-                     int ldc, hipStream_t stream);
+                     int ldc, hipStream_t stream, int kernel = 0);
 // X[m x n] = B[m x n] * W[n x n]^T, W lower triangular with stored zeros
 // above its diagonal. Full 128-blocks and even leading dimensions only
 // (callers dispatch).
 void launch_dtrmm_rlt(int m, int n, const double* B, int ldb, const double* W,
-                      int ldw, double* X, int ldx, hipStream_t stream);
+                      int ldw, double* X, int ldx, hipStream_t stream,
+                      int kernel = 0);
 // The TN family (operands contiguous along K), bounds-checked: any shape and
 // leading dimension. W is lower triangular and whatever is stored above its
 // diagonal is ignored.
@@ -52,13 +57,15 @@ void launch_potf2(double* A, int n, int ld, hipStream_t stream);
 void gpu_gemm_hip(Task& t, GpuTaskCtx& g);
 
 // Host-memory entry points for the Python test bindings: upload, one
-// launch on the null stream, download.
+// launch on the null stream, download. `kernel` as in the launchers.
 void test_dgemm_nt_hip(int m, int n, int k, const double* A, int lda,
-                       const double* B, int ldb, double* C, int ldc);
+                       const double* B, int ldb, double* C, int ldc,
+                       int kernel = 0);
 void test_dsyrk_ln_hip(int n, int k, const double* A, int lda, double* C,
-                       int ldc);
+                       int ldc, int kernel = 0);
 void test_dtrmm_rlt_hip(int m, int n, const double* B, int ldb,
-                        const double* W, int ldw, double* X, int ldx);
+                        const double* W, int ldw, double* X, int ldx,
+                        int kernel = 0);
 void test_dgemm_tn_hip(int m, int n, int k, const double* A, int lda,
                        const double* B, int ldb, double* C, int ldc);
 void test_dgemm_nn_hip(int m, int n, int k, const double* A, int lda,
@@ -71,10 +78,24 @@ void test_dlauum_l_hip(int n, const double* W, int ldw, double* X, int ldx);
 void test_potf2_hip(double* A, int n);
 
 // Timed device-resident launch loops; return seconds for `iters` launches.
-double bench_dgemm_hip(int m, int n, int k, int iters);
+// `kernel` as in the launchers.
+double bench_dgemm_hip(int m, int n, int k, int iters, int kernel = 0);
+double bench_dsyrk_hip(int n, int k, int iters, int kernel = 0);
 // kind 0 gemm (m, n, k), 1 syrk (n, k), 2 trmm (m, n), 3 lauum (n)
 double bench_dgemm_tn_hip(int kind, int m, int n, int k, int iters);
 double bench_dgemm_nn_hip(int m, int n, int k, int iters);
-double bench_dtrmm_hip(int m, int n, int iters);
+double bench_dtrmm_hip(int m, int n, int iters, int kernel = 0);
+
+// The Cholesky DAG's kernel mix at tile size nb, side by side on four
+// non-blocking streams: two loop rocblas_dgemm NT nb^3 (C -= A B^T), 5 *
+// per_round / 2 launches each, one loops the tile SYRK (n = k = nb) and one
+// the TRSM product (m = n = nb), per_round launches each (the DAG's 5:1:1),
+// the hand kinds on `kernel`. One untimed launch of each warms up.
+struct CoresidentTimes {
+  double wall_s;       // host clock, all streams idle at both ends
+  double gemm_s[2];    // first to last event of each stream
+  double syrk_s, trmm_s;
+};
+CoresidentTimes bench_coresident(int nb, int per_round, int kernel = 0);
 
 }  // namespace pa

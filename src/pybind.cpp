@@ -857,9 +857,11 @@ PYBIND11_MODULE(_core, m) {
     return n;
   });
   // Standalone kernel harnesses for GPU numerics tests/debugging.
+  // `kernel` of the three entries below names the full-tile kernel (3 or 4;
+  // 0: PARSEC_MCA_dgemm_nt_kernel); shapes that take another kernel ignore it
   m.def("dgemm_nt_hip", [](py::array_t<double> A, py::array_t<double> B,
                            py::array_t<double> C, int m, int n, int k, int lda,
-                           int ldb, int ldc) {
+                           int ldb, int ldc, int kernel) {
     // C[m x n] -= A[m x k] * B[n x k]^T; column-major buffers flattened 1-D
     // with k / k / n columns of lda / ldb / ldc doubles each (0: the rows)
     if (lda == 0) lda = m;
@@ -870,20 +872,22 @@ PYBIND11_MODULE(_core, m) {
         C.size() < (py::ssize_t)ldc * n)
       throw std::invalid_argument("dgemm_nt_hip: buffer smaller than ld*cols");
     pa::test_dgemm_nt_hip(m, n, k, A.data(), lda, B.data(), ldb,
-                          C.mutable_data(), ldc);
+                          C.mutable_data(), ldc, kernel);
   }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
-     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0,
+     py::arg("kernel") = 0);
   m.def("dsyrk_ln_hip", [](py::array_t<double> A, py::array_t<double> C, int n,
-                           int k, int lda, int ldc) {
+                           int k, int lda, int ldc, int kernel) {
     // C[n x n](lower blocks) -= A[n x k] * A^T; buffers as above
     if (n <= 0 || k <= 0 || lda < n || ldc < n ||
         A.size() < (py::ssize_t)lda * k || C.size() < (py::ssize_t)ldc * n)
       throw std::invalid_argument("dsyrk_ln_hip: buffer smaller than ld*cols");
-    pa::test_dsyrk_ln_hip(n, k, A.data(), lda, C.mutable_data(), ldc);
-  });
+    pa::test_dsyrk_ln_hip(n, k, A.data(), lda, C.mutable_data(), ldc, kernel);
+  }, py::arg("A"), py::arg("C"), py::arg("n"), py::arg("k"), py::arg("lda"),
+     py::arg("ldc"), py::arg("kernel") = 0);
   m.def("dtrmm_rlt_hip", [](py::array_t<double> B, py::array_t<double> W,
                             py::array_t<double> X, int m, int n, int ldb,
-                            int ldw, int ldx) {
+                            int ldw, int ldx, int kernel) {
     // X[m x n] = B[m x n] * W[n x n]^T; column-major buffers flattened 1-D
     // with n columns of ldb / ldw / ldx doubles each
     if (m <= 0 || n <= 0 || ldb < m || ldx < m || ldw < n ||
@@ -891,8 +895,9 @@ PYBIND11_MODULE(_core, m) {
         X.size() < (py::ssize_t)ldx * n)
       throw std::invalid_argument("dtrmm_rlt_hip: buffer smaller than ld*n");
     pa::test_dtrmm_rlt_hip(m, n, B.data(), ldb, W.data(), ldw,
-                           X.mutable_data(), ldx);
-  });
+                           X.mutable_data(), ldx, kernel);
+  }, py::arg("B"), py::arg("W"), py::arg("X"), py::arg("m"), py::arg("n"),
+     py::arg("ldb"), py::arg("ldw"), py::arg("ldx"), py::arg("kernel") = 0);
   // The TN family: operands are k x m / k x n, contiguous along K.
   m.def("dgemm_tn_hip", [](py::array_t<double> A, py::array_t<double> B,
                            py::array_t<double> C, int m, int n, int k, int lda,
@@ -1035,18 +1040,44 @@ PYBIND11_MODULE(_core, m) {
   }, py::arg("A"), py::arg("m"), py::arg("k"), py::arg("lda") = 0,
      py::arg("ts_split") = 0, py::arg("impl") = "hand", py::arg("wgs") = 0,
      py::arg("poolA") = 0, py::arg("apply") = "", py::arg("lookahead") = -1);
-  // ms per launch of the triangular X = B W^T kernel
-  m.def("bench_dtrmm", [](int m, int n, int iters) {
-    return pa::bench_dtrmm_hip(m, n, iters) / iters * 1e3;
-  }, py::call_guard<py::gil_scoped_release>());
+  // ms per launch of the triangular X = B W^T kernel; `kernel` in this and
+  // the next three entries as in dgemm_nt_hip
+  m.def("bench_dtrmm", [](int m, int n, int iters, int kernel) {
+    return pa::bench_dtrmm_hip(m, n, iters, kernel) / iters * 1e3;
+  }, py::arg("m"), py::arg("n"), py::arg("iters"), py::arg("kernel") = 0,
+     py::call_guard<py::gil_scoped_release>());
+  // ms per launch of the hand tile SYRK, C (lower blocks) -= A A^T
+  m.def("bench_dsyrk", [](int n, int k, int iters, int kernel) {
+    return pa::bench_dsyrk_hip(n, k, iters, kernel) / iters * 1e3;
+  }, py::arg("n"), py::arg("k"), py::arg("iters"), py::arg("kernel") = 0,
+     py::call_guard<py::gil_scoped_release>());
   // impl: "hip" (the hand kernel; "v2" is its old name) or "rocblas"
-  m.def("bench_dgemm", [](int m, int n, int k, int iters, std::string impl) {
+  m.def("bench_dgemm", [](int m, int n, int k, int iters, std::string impl,
+                          int kernel) {
     if (impl != "hip" && impl != "v2" && impl != "rocblas")
       throw std::invalid_argument("bench_dgemm: impl is \"hip\" or \"rocblas\"");
-    double dt = impl == "rocblas" ? pa::bench_dgemm_rocblas(m, n, k, iters)
-                                  : pa::bench_dgemm_hip(m, n, k, iters);
+    double dt = impl == "rocblas"
+                    ? pa::bench_dgemm_rocblas(m, n, k, iters)
+                    : pa::bench_dgemm_hip(m, n, k, iters, kernel);
     return 2.0 * m * n * k * iters / dt / 1e12;  // TFLOP/s
-  }, py::call_guard<py::gil_scoped_release>());
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+     py::arg("impl"), py::arg("kernel") = 0,
+     py::call_guard<py::gil_scoped_release>());
+  // The Cholesky DAG's kernel mix side by side (bench_coresident in
+  // kernels_hip.hpp): ms of the whole mix and of each stream
+  m.def("bench_coresident", [](int nb, int per_round, int kernel) {
+    pa::CoresidentTimes t;
+    {
+      py::gil_scoped_release nogil;
+      t = pa::bench_coresident(nb, per_round, kernel);
+    }
+    py::dict r;
+    r["wall_ms"] = t.wall_s * 1e3;
+    r["gemm_ms"] = py::make_tuple(t.gemm_s[0] * 1e3, t.gemm_s[1] * 1e3);
+    r["syrk_ms"] = t.syrk_s * 1e3;
+    r["trmm_ms"] = t.trmm_s * 1e3;
+    return r;
+  }, py::arg("nb") = 4096, py::arg("per_round") = 8, py::arg("kernel") = 0);
   // PCIe/xGMI link probe (reference tools/gpu/testbandwidth analog):
   // pinned-host H2D/D2H and on-device D2D copy bandwidth in GB/s.
   m.def("hip_bandwidth", [](size_t nbytes, int iters) {
