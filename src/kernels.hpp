@@ -151,6 +151,9 @@ enum TaskClassId : int {
   // kernels_inv.cpp
   TC_INV_TRSM_R = 80, TC_TRTRI_INPLACE = 81, TC_SYRK_T = 82, TC_GEMM_TN = 83,
   TC_TRMM_LLT = 84, TC_LAUUM = 85,
+  // kernels_f32.cpp
+  TC_SPOTRF = 90, TC_STRTRI = 91, TC_STRSM = 92, TC_STRSM_INV = 93,
+  TC_SSYRK = 94, TC_SGEMM = 95, TC_CONVERT = 96,
   // pybind.cpp
   TC_PY_TASK = 100,
 };
@@ -188,6 +191,13 @@ TaskClass& tc_tsmqr();
 void insert_spd_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_full_fill(Dtd& tp, TiledMatrix& A, uint32_t seed);
 void insert_potrf(Dtd& tp, TiledMatrix& A);
+// insert_potrf in single precision on the fp32 hand kernels: A holds 4-byte
+// elements (kernels_f32.cpp).
+void insert_potrf_f32(Dtd& tp, TiledMatrix& A);
+// Dst = Src element by element between fp64 and fp32 (8 -> 4 rounds to
+// nearest even), same shape, tiling and grid; one task per tile of Src that
+// holds data (kernels_f32.cpp).
+void insert_convert(Dtd& tp, TiledMatrix& Src, TiledMatrix& Dst);
 // Householder tile QR, M >= N: R in the upper tiles, reflectors not kept.
 void insert_geqrf(Dtd& tp, TiledMatrix& A);
 // QR by block Gram-Schmidt with CholeskyQR2 panels (matrix-core rates;

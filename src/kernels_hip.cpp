@@ -53,6 +53,7 @@
 #include "gpu_blas.hpp"
 #include "kernels.hpp"
 #include "kernels_bench.hpp"
+#include "kernels_blocks.hpp"
 
 namespace pa {
 
@@ -73,37 +74,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // which hides each one's staging under the other's MFMA phase (fp64 MFMA
 // issue is 64 cyc/SIMD, so 4 co-resident waves/SIMD keep the matrix pipe
 // fed without hand pipelining).
-
-// 1-D grid with a bijective XCD-aware remap so consecutive blocks share B
-// panels within one XCD's L2 (guide T1).
-__device__ __forceinline__ int xcd_swizzle(int id, int nwg) {
-  int q = nwg >> 3, r = nwg & 7;
-  int xcd = id & 7, pos = id >> 3;
-  // blocks per XCD: first r XCDs get q+1
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-}
-
-// id -> (i >= j) over a lower-triangular set enumerated row by row.
-__device__ __forceinline__ void tri_decode(int id, int& i, int& j) {
-  i = 0;
-  while (id > i) { i++; id -= i; }
-  j = id;
-}
-
-// This block's (bx, by): in the nbx-wide full grid, or in the lower block
-// set (SYRK writes only the lower blocks; diagonal blocks compute their
-// full tile: the upper half of a diagonal tile is symmetric-valid and never
-// read by the DAG).
-__device__ __forceinline__ void block_decode(bool tri, int nbx, int& bx,
-                                             int& by) {
-  int id = xcd_swizzle(blockIdx.x, gridDim.x);
-  if (tri) {
-    tri_decode(id, bx, by);
-  } else {
-    bx = id % nbx;
-    by = id / nbx;
-  }
-}
 
 // One DEPTH-deep K-tile into the wave's 2x4 accumulators. ap / bp point at
 // this lane's element of the first A / B fragment in a [k][row] LDS image
@@ -521,20 +491,6 @@ __global__ void k_dgemm_nn(int m, int n, int k, const double* __restrict__ A,
 }
 
 // ------------------------------------------------------------- launchers
-// Every kernel here asks for more dynamic LDS than a launch gets by
-// default: raise that kernel's limit once, then launch.
-template <auto Kern, typename... Args>
-static void launch_lds(int grid, int block, size_t lds, hipStream_t stream,
-                       Args... args) {
-  static const bool raised = [lds] {
-    PA_HIP_CHECK(hipFuncSetAttribute(
-        (const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return true;
-  }();
-  (void)raised;
-  hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, stream, args...);
-}
-
 constexpr size_t LDS_V2 = 4 * BKD * 129 * 8;
 constexpr size_t LDS_V3 = 2 * BKD * (BM + BN) * 8;
 constexpr size_t LDS_V4 = V4_S * V4_BK * (BM + BN) * 8;

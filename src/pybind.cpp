@@ -18,6 +18,7 @@
 #include "gpu_graph.hpp"
 #include "kernels.hpp"
 #include "kernels_bench.hpp"
+#include "kernels_f32.hpp"
 #include "kernels_hip.hpp"
 #include "pins.hpp"
 #include "profiling.hpp"
@@ -425,6 +426,10 @@ PYBIND11_MODULE(_core, m) {
         py::arg("seed") = 42u, py::call_guard<py::gil_scoped_release>());
   m.def("insert_potrf", &insert_potrf, py::arg("tp"), py::arg("A"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("insert_potrf_f32", &insert_potrf_f32, py::arg("tp"), py::arg("A"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("insert_convert", &insert_convert, py::arg("tp"), py::arg("src"),
+        py::arg("dst"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_getrf_nopiv", &insert_getrf_nopiv, py::arg("tp"),
         py::arg("A"), py::call_guard<py::gil_scoped_release>());
   m.def("insert_geqrf", &insert_geqrf, py::arg("tp"), py::arg("A"),
@@ -1063,6 +1068,69 @@ PYBIND11_MODULE(_core, m) {
   }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
      py::arg("impl"), py::arg("kernel") = 0,
      py::call_guard<py::gil_scoped_release>());
+  // The fp32 kernels (kernels_f32.cpp): float32 buffers, arguments as in
+  // dgemm_nt_hip, dsyrk_ln_hip and dtrmm_rlt_hip without the selector.
+  m.def("sgemm_nt_hip", [](py::array_t<float> A, py::array_t<float> B,
+                           py::array_t<float> C, int m, int n, int k, int lda,
+                           int ldb, int ldc) {
+    if (lda == 0) lda = m;
+    if (ldb == 0) ldb = n;
+    if (ldc == 0) ldc = m;
+    if (m <= 0 || n <= 0 || k <= 0 || lda < m || ldb < n || ldc < m ||
+        A.size() < (py::ssize_t)lda * k || B.size() < (py::ssize_t)ldb * k ||
+        C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("sgemm_nt_hip: buffer smaller than ld*cols");
+    pa::test_sgemm_nt_hip(m, n, k, A.data(), lda, B.data(), ldb,
+                          C.mutable_data(), ldc);
+  }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("m"), py::arg("n"),
+     py::arg("k"), py::arg("lda") = 0, py::arg("ldb") = 0, py::arg("ldc") = 0);
+  m.def("ssyrk_ln_hip", [](py::array_t<float> A, py::array_t<float> C, int n,
+                           int k, int lda, int ldc) {
+    if (n <= 0 || k <= 0 || lda < n || ldc < n ||
+        A.size() < (py::ssize_t)lda * k || C.size() < (py::ssize_t)ldc * n)
+      throw std::invalid_argument("ssyrk_ln_hip: buffer smaller than ld*cols");
+    pa::test_ssyrk_ln_hip(n, k, A.data(), lda, C.mutable_data(), ldc);
+  }, py::arg("A"), py::arg("C"), py::arg("n"), py::arg("k"), py::arg("lda"),
+     py::arg("ldc"));
+  m.def("strmm_rlt_hip", [](py::array_t<float> B, py::array_t<float> W,
+                            py::array_t<float> X, int m, int n, int ldb,
+                            int ldw, int ldx) {
+    if (m <= 0 || n <= 0 || ldb < m || ldx < m || ldw < n ||
+        B.size() < (py::ssize_t)ldb * n || W.size() < (py::ssize_t)ldw * n ||
+        X.size() < (py::ssize_t)ldx * n)
+      throw std::invalid_argument("strmm_rlt_hip: buffer smaller than ld*n");
+    pa::test_strmm_rlt_hip(m, n, B.data(), ldb, W.data(), ldw,
+                           X.mutable_data(), ldx);
+  }, py::arg("B"), py::arg("W"), py::arg("X"), py::arg("m"), py::arg("n"),
+     py::arg("ldb"), py::arg("ldw"), py::arg("ldx"));
+  // dst[rows x cols] = src converted, column-major buffers of cols columns,
+  // ld elements each, on both sides: fp64 -> fp32 and fp32 -> fp64
+  m.def("convert_d2s_hip", [](py::array_t<double> src, py::array_t<float> dst,
+                              int rows, int cols, int ld) {
+    if (rows <= 0 || cols <= 0 || ld < rows ||
+        src.size() < (py::ssize_t)ld * cols ||
+        dst.size() < (py::ssize_t)ld * cols)
+      throw std::invalid_argument("convert_d2s_hip: buffer smaller than ld*cols");
+    pa::test_convert_d2s_hip(src.data(), dst.mutable_data(), rows, cols, ld);
+  }, py::arg("src"), py::arg("dst"), py::arg("rows"), py::arg("cols"),
+     py::arg("ld"));
+  m.def("convert_s2d_hip", [](py::array_t<float> src, py::array_t<double> dst,
+                              int rows, int cols, int ld) {
+    if (rows <= 0 || cols <= 0 || ld < rows ||
+        src.size() < (py::ssize_t)ld * cols ||
+        dst.size() < (py::ssize_t)ld * cols)
+      throw std::invalid_argument("convert_s2d_hip: buffer smaller than ld*cols");
+    pa::test_convert_s2d_hip(src.data(), dst.mutable_data(), rows, cols, ld);
+  }, py::arg("src"), py::arg("dst"), py::arg("rows"), py::arg("cols"),
+     py::arg("ld"));
+  // TFLOP/s of C -= A B^T in fp32: impl "hip" (the hand kernel) or "rocblas"
+  m.def("bench_sgemm", [](int m, int n, int k, int iters, std::string impl) {
+    if (impl != "hip" && impl != "rocblas")
+      throw std::invalid_argument("bench_sgemm: impl is \"hip\" or \"rocblas\"");
+    double dt = pa::bench_sgemm(m, n, k, iters, impl == "rocblas");
+    return 2.0 * m * n * k * iters / dt / 1e12;
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("iters"),
+     py::arg("impl"), py::call_guard<py::gil_scoped_release>());
   // The Cholesky DAG's kernel mix side by side (bench_coresident in
   // kernels_hip.hpp): ms of the whole mix and of each stream
   m.def("bench_coresident", [](int nb, int per_round, int kernel) {
